@@ -18,12 +18,24 @@ Timing: W untimed warm-up steps, then the K-step region — bracketed by barrier
 torch.cuda.synchronize() on both sides, maximum over ranks — is run `repeats` times, every
 repeat doing the full work into freshly reserved history rows; `value` comes from the MEDIAN
 repeat, the spread is reported (`timed_region_ms`).  A 20-step region is ~80 us: one sample
-of it is mostly host jitter.
+of it is mostly host jitter.  By default the count follows K alone (3 to 20 repeats), so the
+steps before the outputs never depend on timing.
 
-Rank 0 prints ONE JSON line: the contract fields plus
+Rank 0 prints ONE JSON line: the contract fields (`ms_per_step` = the median region / K) plus
   roofline      the dominant kernel (the PlaceCells rate kernel): algorithmic bytes per launch /
-                its average duration, measured with HIP events on the stream it runs on
+                its average duration, from the timed regions themselves
+
+A plain run does only that: set-up, warm-up, the timed regions, the outputs (--dump-outputs), the line.
+`--full` adds what takes runs of its own: HIP events on the dominant kernel in ten more regions, the
+closed-loop plans in one native call, the chip's measured store ceiling, the `secondary` block (the other
+configurations and forms, cfg2 line only) and
   cpu_baseline  the float64 NumPy oracle of the same path timed on the host cores (rank 0, N=1)
+
+--dump-outputs DIR writes, right after the timed regions, what the timed path left for its caller after
+its last step (rank 0): the agents' state (float64), the last trajectory row of simulate() (float32) and
+every population's firing rates (float32; a fixed, seeded sample of agent columns where one population's
+rates exceed 4 M values), as DIR/<name>.npy.  The same arguments give the same inputs and the same number of
+steps on every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -361,9 +373,37 @@ def relaunch_as_ranks(args):
     return subprocess.call(cmd, env=env)
 
 
-def measure(args, config, K, W, repeats, rank, world, local, dist, ctrl_on_cpu, control_plane, store_ceiling=True):
+DUMP_VALUES_PER_POPULATION = 4 << 20   # (16 MB of float32 rates: a cfg-2 row whole; at most 56 MB over the populations)
+DUMP_VALUES_IN_ALL = 14 << 20
+
+
+def dump_outputs(path, ag, pops, traj):
+    """What the timed path left for its caller after its last step, as <name>.npy in `path` (float64 / float32)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.asarray(getattr(ag, k), dtype=np.float64)
+           for k in ("pos", "velocity", "rotational_velocity", "measured_velocity", "head_direction", "distance_travelled")}
+    B = int(ag.n_agents)
+    if traj is not None:   # (simulate(): the last row of the trajectory history it returned, [8, B])
+        out["trajectory_last_step"] = traj[-1, :, :B].float().cpu().numpy()
+    cap = min(DUMP_VALUES_PER_POPULATION, DUMP_VALUES_IN_ALL // max(1, len(pops)))
+    for i, p in enumerate(pops):
+        fr = p.firingrate_tensor[:, :B]
+        n = int(fr.shape[0])
+        if n * B > cap:    # a fixed, seeded sample of agent columns (the same on every run and every build)
+            cols = np.sort(np.random.default_rng(1000 + i).choice(B, max(1, cap // n), replace=False))
+            fr = fr[:, torch.from_numpy(cols).to(fr.device)]
+        out[f"rates_{i}_{type(p).__name__}"] = fr.float().cpu().numpy()
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def measure(args, config, K, W, repeats, rank, world, local, dist, ctrl_on_cpu, control_plane, store_ceiling=True,
+            full=False, dump_dir=None):
     """One configuration: build the world, W warm-up steps, `repeats` timed K-step regions; the contract's fields
-    (rank 0; None elsewhere) and the configuration."""
+    (rank 0; None elsewhere) and the configuration.  `full`: the extra runs (events on the dominant kernel, the plans in
+    one native call, the store ceiling); `dump_dir`: rank 0's outputs after the last timed step (dump_outputs)."""
     import numpy as np
     import torch
     import ratinabox_amd as riab
@@ -420,6 +460,8 @@ def measure(args, config, K, W, repeats, rank, world, local, dist, ctrl_on_cpu, 
             else:
                 plan["p"] = ag.make_step_plan(capacity=max(K, W))
 
+    last = {"traj": None}   # (--dump-outputs: what simulate() returned last, the trajectory rows of the call)
+
     def run(n_steps):
         if args.plan:
             prepare()
@@ -434,7 +476,8 @@ def measure(args, config, K, W, repeats, rank, world, local, dist, ctrl_on_cpu, 
                 for p in pops:
                     p.update()
         else:
-            ag.simulate(n_steps, chunk=chunk)
+            traj = ag.simulate(n_steps, chunk=chunk)
+            last["traj"] = traj if (dump_dir and ag.save_history) else None
 
     def barrier():
         if dist is not None:
@@ -503,11 +546,14 @@ def measure(args, config, K, W, repeats, rank, world, local, dist, ctrl_on_cpu, 
         if fused_mode or native_mode:
             kernel_ms.append(ag.last_rate_kernel_ms())
             kernel_units.append(getattr(ag, "_last_fused_units", B * K))  # (rings: the last ring-length piece of the run)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, ag, pops, last["traj"])
+    last["traj"] = None
     # the closed-loop plans once more with ALL K steps in one native call per region (`plan.step(K)`: no per-step action
     # from the host, the step kernels back to back at the device's pace) — not part of `value`: how far the one-call-per-
     # step figure above is from the kernels themselves
     one_call_us = None
-    if args.plan and not args.per_step and rank == 0 and K > 1:
+    if full and args.plan and not args.per_step and rank == 0 and K > 1:
         oc = []
         for _r in range(5):
             fresh_history(K)
@@ -522,7 +568,7 @@ def measure(args, config, K, W, repeats, rank, world, local, dist, ctrl_on_cpu, 
     # with HIP start / stop events attached to the kernel's launch (what rocprofv3 would report for it)
     event_ms = []
     one_kernel = fused_mode and ag.last_rate_stage_form() == "one-kernel"   # (what the library chose: riab_streamer_last_form)
-    if one_kernel and ag._time_rate_kernel is True:
+    if full and one_kernel and ag._time_rate_kernel is True:
         ag._time_rate_kernel = "events"
         for _r in range(10):
             fresh_history(K)
@@ -669,7 +715,9 @@ def measure(args, config, K, W, repeats, rank, world, local, dist, ctrl_on_cpu, 
                 roofline["frac_device_clock"] = round(unit_bytes * avg_units / (cm * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
             else:
                 roofline["timed_by"] = ("the device's constant clock (s_memrealtime) read by the kernel's first-row waves at "
-                                        "their start and its last-row waves once their stores are acknowledged")
+                                        "their start and its last-row waves once their stores are acknowledged, in the timed "
+                                        "regions (no dispatch ramp, no write-back at the end: 5-10 % shorter than the HIP events "
+                                        "on the launch that `--full` reports as `avg_launch_ms`)")
         if fused_mode:
             roofline["note"] = ("the rate stage runs concurrently with the trajectory kernel whose rows it consumes (coupled "
                                 "by flags in device memory, one native call per timed region): its duration includes "
@@ -717,7 +765,7 @@ def measure(args, config, K, W, repeats, rank, world, local, dist, ctrl_on_cpu, 
 
     # the chip's measured store ceiling in this same process (riab_fill: one float4 per thread,
     # address-ordered), for context next to the spec peak
-    if rank == 0 and roofline is not None and store_ceiling:
+    if full and rank == 0 and roofline is not None and store_ceiling:
         L = riab._lib
         nbytes = 1 << 30
         buf = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
@@ -792,11 +840,12 @@ def measure(args, config, K, W, repeats, rank, world, local, dist, ctrl_on_cpu, 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=1024, help="steps of one timed region (K)")
     ap.add_argument("--warmup", type=int, default=128)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--chunk", type=int, default=128, help="steps per kernel launch in the chunked two-stream path")
-    ap.add_argument("--repeats", type=int, default=0, help="repeats of the timed K-step region (0 = by K)")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="repeats of the timed K-step region (0 = by K: 3 to 20)")
     ap.add_argument("--per-step", action="store_true", help="time the drop-in per-step API instead of simulate()")
     ap.add_argument("--plan", action="store_true", help="time the closed-loop path through a native step plan")
     ap.add_argument("--plan-batch", type=int, default=1, help="steps per riab_plan_step call (1 = closed loop)")
@@ -808,7 +857,12 @@ def main():
                          "reference's multi-agent environment with agentmode='interact')")
     ap.add_argument("--strict", action="store_true",
                     help="simulate() in the mode of riab_simulate that meets SURVEY 8(b2) to the letter (include/riab_hip.h 'Two modes')")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: HIP events on the dominant kernel, the plans in one native call, "
+                         "the store ceiling, the `secondary` block and the CPU baseline (default: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: the config's agents are the TOTAL, split over the ranks (default: weak scaling, "
                          "the config's agents per GPU)")
@@ -817,7 +871,7 @@ def main():
                     help="bring the process group (RCCL control plane: barriers + the max-reduce of the timings) up even "
                          "for one rank, when launched by torch.distributed.run (a one-GPU test of the multi-GPU launch form)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the short cfg3 / cfg4 / cfg5 runs reported in the `secondary` block of the cfg2 line")
+                    help="with --full: skip the short cfg3 / cfg4 / cfg5 runs reported in the `secondary` block of the cfg2 line")
     ap.add_argument("--secondary-timeout", type=float, default=240.0,
                     help="seconds after which the secondary block is abandoned and the headline line printed without it")
     ap.add_argument("--no-bind", action="store_true",
@@ -894,7 +948,7 @@ def main():
                 control_plane = "gloo"
 
     out, cfg = measure(args, args.config, args.steps, args.warmup, args.repeats, rank, world, local, dist, ctrl_on_cpu if dist
-                       is not None else False, control_plane)
+                       is not None else False, control_plane, full=args.full, dump_dir=args.dump_outputs)
     if dist is not None:   # every rank's placement in rank 0's line
         allb = [None] * world
         dist.all_gather_object(allb, args.host_binding)
@@ -929,7 +983,7 @@ def main():
     dog = threading.Timer(args.secondary_timeout, bail)
     dog.daemon = True
     sec_steps = 256 if share else SECONDARY_STEPS   # (the test hook: N ranks' histories on ONE GPU)
-    if args.config == "cfg2" and not (args.no_secondary or args.per_step or args.plan or args.task or args.strong):
+    if args.full and args.config == "cfg2" and not (args.no_secondary or args.per_step or args.plan or args.task or args.strong):
         dog.start()
         saved = args.no_history
         # ... and the CLOSED-LOOP forms of cfg2 (the reference's per-step API, Agent.py:160-242 + Neurons.py:145-171, and
@@ -959,7 +1013,7 @@ def main():
             try:
                 steps_here = args.steps if mode == "strict" else 256 if mode in ("plan", "per_step", "task", "task_world") else sec_steps
                 o, c = measure(args, name, steps_here, warm, 0 if mode == "strict" else 5, rank, world, local, dist,
-                               ctrl_on_cpu if dist is not None else False, control_plane, store_ceiling=False)
+                               ctrl_on_cpu if dist is not None else False, control_plane, store_ceiling=False, full=True)
             except Exception as e:  # noqa: BLE001  (the headline line must not be lost to a secondary run)
                 secondary[key] = {"error": f"{type(e).__name__}: {e}"}
                 continue
@@ -997,7 +1051,7 @@ def main():
                 # 45 %: the figure the >= 7x-at-8-GPUs clause is ALSO read from
                 out["value_T1024"] = t1024["value"]
                 out["frac_whole_path_T1024"] = t1024.get("frac_whole_path")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out), flush=True)
     if dist is not None:

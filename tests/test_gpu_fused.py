@@ -746,9 +746,10 @@ def _bench(args, extra_env=None, timeout=900):
 
 
 def test_bench_contract_line_on_the_drivers_command(riab):
-    """`bench.py --gpus 1 --steps 20 --warmup 5` must carry a non-null roofline whose numbers are
-    consistent with the line's own value."""
-    out = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"])
+    """the driver's command with `--full` (`bench.py --gpus 1 --steps 20 --warmup 5 --full`) must carry a
+    roofline whose numbers — HIP events in extra regions, the device clock beside them — are consistent with the line's own
+    value.  The plain command's roofline: test_bench_plain_line_and_dumped_outputs."""
+    out = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--full"])
     assert out["n_gpus"] == 1 and out["steps"] == 20 and out["warmup"] == 5 and out["repeats"] >= 3
     rf = out["roofline"]
     # (the kernel's duration: HIP events in ten extra regions; the device-clock figure of the timed regions beside it)
@@ -759,6 +760,55 @@ def test_bench_contract_line_on_the_drivers_command(riab):
     assert rf["avg_launch_ms"] <= out["timed_region_ms"]["max"]
     assert out["diagnostics"].get("pipeline_timeouts", 0) == 0
     assert abs(out["value"] - 4096 * 20 / (out["timed_region_ms"]["median"] * 1e-3)) / out["value"] < 1e-3
+
+
+@pytest.mark.parametrize("steps", [20, 16384])
+def test_bench_plain_line_and_dumped_outputs(riab, tmp_path, steps):
+    """A plain run prints the headline line alone (no extra runs: `secondary`, `cpu_baseline`, the store ceiling are
+    `--full`'s) with a roofline from the timed regions, and `--dump-outputs DIR` writes the same float32 / float64
+    arrays, at most 64 MB, on every run: the last timed step's output (the rates match the oracle at the dumped
+    positions).  At 16384 steps — regions of a large fraction of a second, the rates through ring buffers — the repeats
+    still follow K alone: the dumped step does not depend on timing."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = _bench(["--gpus", "1", "--steps", str(steps), "--warmup", "5", "--dump-outputs", str(d)])
+        assert out["steps"] == steps and out["warmup"] == 5 and out["ms_per_step"] > 0
+        assert out["repeats"] == (20 if steps == 20 else 3)   # (by K alone: max(3, min(20, 4096 // K)))
+        assert abs(out["ms_per_step"] - out["timed_region_ms"]["median"] / steps) < 1e-5
+        assert not {"secondary", "cpu_baseline", "value_T1024"} & set(out)
+        rf = out["roofline"]
+        assert rf is not None and rf["bound"] == "hbm" and 0.0 < rf["frac"] <= 1.0 and "measured_store_ceiling_GBps" not in rf
+        if steps == 20:   # (the one-kernel form, timed by the device clock; a ring-buffer run reports its last ring piece)
+            assert rf["units_per_launch"] == 4096 * steps and "device's constant clock" in rf["timed_by"]
+        else:
+            assert rf["units_per_launch"] % 4096 == 0 and 0 < rf["units_per_launch"] <= 4096 * steps
+        files = sorted(d.glob("*.npy"))
+        arrays = {f.stem: np.load(f) for f in files}
+        assert {"pos", "head_direction", "rates_0_PlaceCells"} <= set(arrays), sorted(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        assert arrays["rates_0_PlaceCells"].shape == (1024, 4096) and np.isfinite(arrays["rates_0_PlaceCells"]).all()
+        if "trajectory_last_step" in arrays:   # (a full history: the row simulate() returned last = the agents' state)
+            assert np.array_equal(arrays["trajectory_last_step"][0:2].T, arrays["pos"].astype(np.float32))
+        else:
+            assert out["config"]["history"] == "ring"
+        runs.append(arrays)
+    for k, a in runs[0].items():
+        assert np.array_equal(a, runs[1][k]), k
+    # the rates are those of the LAST step: PlaceCells at the dumped positions (float32 rows, as the kernel reads them)
+    _env, ag, pops = bench.build_world(riab, bench.CONFIGS["cfg2"], 0)
+    centres, widths = pops[0].place_cell_centres, pops[0].place_cell_widths
+    del _env, ag, pops
+    cols = np.arange(0, 4096, 97)
+    pos32 = runs[0]["pos"][cols].astype(np.float32).astype(np.float64)
+    ref = orc.place_cells(orc.EnvSpec(), pos32, centres, widths)
+    np.testing.assert_allclose(runs[0]["rates_0_PlaceCells"][:, cols], ref, rtol=1e-5, atol=1e-30)
 
 
 def bench_cpus(text):
@@ -773,7 +823,7 @@ def bench_cpus(text):
 def test_bench_launches_its_own_ranks(riab):
     """`python bench.py --gpus 2` (no launcher) must start two ranks and say so.  Both ranks share
     this box's one GPU (RIAB_BENCH_SHARE_GPU: gloo control plane), which exercises everything but RCCL."""
-    out = _bench(["--gpus", "2", "--steps", "64", "--warmup", "8", "--no-cpu-baseline", "--secondary-timeout", "150"],
+    out = _bench(["--gpus", "2", "--steps", "64", "--warmup", "8", "--no-cpu-baseline", "--secondary-timeout", "150", "--full"],
                  {"RIAB_BENCH_SHARE_GPU": "1"}, timeout=400)
     assert "secondary_error" not in out, out["secondary_error"]
     assert out["n_gpus"] == 2 and out["steps"] == 64

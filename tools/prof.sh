@@ -31,31 +31,31 @@ if [ "$2" = "world" ]; then  # only the one-world task (`bash tools/prof.sh r05 
   cut -d, -f1-7 $O/${R}_task_world_kernel_stats.csv | cut -c1-170 | sed -n 1,8p
   exit 0
 fi
-timeout 400 python $B --gpus 1 --steps 20 --warmup 5 > $O/${R}_driver_bench_line.json 2> /dev/null
-run_trace driver --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline
-run_pmc driver WRITE_SIZE --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary
-run_pmc driver FETCH_SIZE --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary
+timeout 400 python $B --gpus 1 --steps 20 --warmup 5 --full > $O/${R}_driver_bench_line.json 2> /dev/null
+run_trace driver --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --full
+run_pmc driver WRITE_SIZE --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --full
+run_pmc driver FETCH_SIZE --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --full
 if [ "$2" = "driver" ]; then  # only the driver's command (`bash tools/prof.sh r05 driver`): line, trace, PMC traffic
   cd $GRAFT_REPO_ROOT
   python tools/pmc_summary.py $O/${R}_driver_pmc_WRITE_SIZE.csv $O/${R}_driver_pmc_FETCH_SIZE.csv --kernel rate_kernel_gated --units-per-launch 81920 --out $O/${R}_pmc_traffic_driver.json > /dev/null 2>&1 && grep -E '"(hbm_bytes_per_unit|traffic_over_algorithmic_kernel|grid_threads)"' $O/${R}_pmc_traffic_driver.json
   exit 0
 fi
-run_trace plan --plan --steps 256 --warmup 32 --no-cpu-baseline --no-secondary
-run_pmc plan WRITE_SIZE --plan --steps 256 --warmup 32 --no-cpu-baseline --no-secondary --repeats 3
-run_pmc plan FETCH_SIZE --plan --steps 256 --warmup 32 --no-cpu-baseline --no-secondary --repeats 3
-run_trace task --task --steps 256 --warmup 32 --no-cpu-baseline --no-secondary
-run_pmc task WRITE_SIZE --task --steps 256 --warmup 32 --no-cpu-baseline --no-secondary --repeats 3
-run_pmc task FETCH_SIZE --task --steps 256 --warmup 32 --no-cpu-baseline --no-secondary --repeats 3
-run_trace cfg3 --config cfg3 --no-cpu-baseline --steps 256 --warmup 32
-run_trace cfg5 --config cfg5 --no-cpu-baseline --steps 256 --warmup 32
+run_trace plan --plan --steps 256 --warmup 32 --no-cpu-baseline --no-secondary --full
+run_pmc plan WRITE_SIZE --plan --steps 256 --warmup 32 --no-cpu-baseline --no-secondary --repeats 3 --full
+run_pmc plan FETCH_SIZE --plan --steps 256 --warmup 32 --no-cpu-baseline --no-secondary --repeats 3 --full
+run_trace task --task --steps 256 --warmup 32 --no-cpu-baseline --no-secondary --full
+run_pmc task WRITE_SIZE --task --steps 256 --warmup 32 --no-cpu-baseline --no-secondary --repeats 3 --full
+run_pmc task FETCH_SIZE --task --steps 256 --warmup 32 --no-cpu-baseline --no-secondary --repeats 3 --full
+run_trace cfg3 --config cfg3 --no-cpu-baseline --steps 256 --warmup 32 --full
+run_trace cfg5 --config cfg5 --no-cpu-baseline --steps 256 --warmup 32 --full
 # (round 6) the closed loops of cfg 3 / cfg 5 (one step1 kernel + the boundary vector cells per step), the one-world task
 # (one step1_task_kernel per step), cfg 3 in the 64-wall room at 1024 steps (the trajectory kernel's wall loops)
-run_trace cfg3_plan --config cfg3 --plan --no-cpu-baseline --no-secondary --steps 256 --warmup 32
-run_trace cfg5_plan --config cfg5 --plan --no-cpu-baseline --no-secondary --steps 256 --warmup 32
-run_trace task_world --task-world --no-cpu-baseline --no-secondary --steps 256 --warmup 32
-run_trace cfg3_64w --config cfg3_64w --no-cpu-baseline --no-secondary --steps 1024 --warmup 32
-run_trace cfg3_1024 --config cfg3 --no-cpu-baseline --no-secondary --steps 1024 --warmup 32
-run_trace cfg5_1024 --config cfg5 --no-cpu-baseline --no-secondary --steps 1024 --warmup 32
+run_trace cfg3_plan --config cfg3 --plan --no-cpu-baseline --no-secondary --steps 256 --warmup 32 --full
+run_trace cfg5_plan --config cfg5 --plan --no-cpu-baseline --no-secondary --steps 256 --warmup 32 --full
+run_trace task_world --task-world --no-cpu-baseline --no-secondary --steps 256 --warmup 32 --full
+run_trace cfg3_64w --config cfg3_64w --no-cpu-baseline --no-secondary --steps 1024 --warmup 32 --full
+run_trace cfg3_1024 --config cfg3 --no-cpu-baseline --no-secondary --steps 1024 --warmup 32 --full
+run_trace cfg5_1024 --config cfg5 --no-cpu-baseline --no-secondary --steps 1024 --warmup 32 --full
 cd $GRAFT_REPO_ROOT
 python tools/pmc_summary.py $O/${R}_driver_pmc_WRITE_SIZE.csv $O/${R}_driver_pmc_FETCH_SIZE.csv --kernel rate_kernel_gated --units-per-launch 81920 --out $O/${R}_pmc_traffic_driver.json > /dev/null 2>&1 && grep -E '"(hbm_bytes_per_unit|traffic_over_algorithmic_kernel|grid_threads)"' $O/${R}_pmc_traffic_driver.json
 python tools/pmc_summary.py $O/${R}_plan_pmc_WRITE_SIZE.csv $O/${R}_plan_pmc_FETCH_SIZE.csv --kernel step1_kernel --units-per-launch 4096 --out $O/${R}_pmc_traffic_plan.json > /dev/null 2>&1 && grep -E '"(hbm_bytes_per_unit|traffic_over_algorithmic_kernel|grid_threads)"' $O/${R}_pmc_traffic_plan.json
