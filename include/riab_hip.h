@@ -353,7 +353,9 @@ int riab_spikes(const RiabRateIO* io, int32_t n, riab_stream_t stream);
 /* Neurons.update noise (Neurons.py:153-168) for T consecutive steps: for each time row t,
  * noise += OU(noise; 0, noise_std, noise_coherence_time) and rates[t][c][b] += noise[c][b].
  * noise device float32 [n][B] read/written; rates device float32 [T][n][B]; z_in device
- * float32 [T][n][B] standard normals or NULL => Philox keyed by (seed; step+t, cell, agent).
+ * float32 [T][n][B] standard normals or NULL => in-kernel draws: one Philox4x32-7 call (the
+ * spike streams' generator) per (cell, 4 agents), counter (step+t, cell, agent_id/4,
+ * RIAB_TAG_NOISE ^ pop_id), key seed; two Box-Muller pairs in fp32 (oracle: noise_normals).
  * theta_dt = dt/tau, sigma_dt = sqrt(2 std^2/(tau dt)) * dt (utils.py:361-368). */
 int riab_neuron_noise(float* noise, float* rates, const float* z_in, int32_t n, int64_t B, int32_t T,
                       float theta_dt, float sigma_dt, uint64_t seed, uint64_t step, int32_t pop_id,
@@ -452,6 +454,9 @@ int riab_plan_set_motion(RiabPlan* plan, const RiabMotion* motion, const double*
 int riab_plan_set_forced(RiabPlan* plan, const double* forced, int64_t n_rows);
 int riab_plan_set_agent_history(RiabPlan* plan, float* hist_base, int64_t capacity_rows);
 int riab_plan_add(RiabPlan* plan, const RiabPopulation* pop);  /* returns the population's index */
+/* the OU constants (RiabPopulation.noise_theta_dt / noise_sigma_dt) of population `index`, which has noise, for the
+ * steps that follow: a plan stepped at another dt than the one it was built at; RIAB_EINVAL for a noiseless one */
+int riab_plan_set_noise(RiabPlan* plan, int32_t index, float theta_dt, float sigma_dt);
 int riab_plan_set_population_history(RiabPlan* plan, int32_t index, float* rates_base, uint8_t* spikes_base,
                                      int64_t capacity_rows);
 int64_t riab_plan_rows_free(const RiabPlan* plan);

@@ -782,9 +782,16 @@ PHILOX_W0 = 0x9E3779B9
 PHILOX_W1 = 0xBB67AE85
 TAG_MOTION = 0x4D4F5449
 TAG_SPIKES = 0x53504B00
+TAG_NOISE = 0x4E4F4900
 
 
-SPIKE_ROUNDS = 7   # the spike streams' Philox4x32-7 (the motion / noise / task streams: -10); csrc/riab_device.h
+SPIKE_ROUNDS = 7   # the spike and neuron-noise streams' Philox4x32-7 (the motion / task streams: -10); csrc/riab_device.h
+
+
+def stream_tag(base, pop_id):
+    """The fourth counter word of a population's spike / noise stream (csrc/riab_device.h stream_tag): the base XOR the
+    population's index, so every population keeps a stream of its own (the bases' low byte is zero)."""
+    return (base ^ int(pop_id)) & 0xFFFFFFFF
 
 
 def philox4x32_10(c0, c1, c2, c3, k0, k1, rounds=10):
@@ -839,10 +846,47 @@ def spike_uniforms(seed, step, pop_id, n_cells, n_agents, agent_id0=0):
     assert agent_id0 % 4 == 0 and n_agents % 4 == 0
     g = (np.arange(n_agents // 4, dtype=np.uint64) + np.uint64(agent_id0 // 4))[None, :]
     cell = np.arange(n_cells, dtype=np.uint64)[:, None]
-    xs = philox4x32_10(step & 0xFFFFFFFF, cell, g, TAG_SPIKES | (pop_id & 0xFF),
+    xs = philox4x32_10(step & 0xFFFFFFFF, cell, g, stream_tag(TAG_SPIKES, pop_id),
                        seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, rounds=SPIKE_ROUNDS)
     u = np.stack([(x >> np.uint32(8)).astype(np.float32) * np.float32(2.0**-24) for x in xs], axis=-1)
     return u.reshape(n_cells, n_agents)
+
+
+def noise_normals(seed, step, pop_id, n_cells, n_agents, agent_id0=0):
+    """The standard normals the device draws for Neurons.update's OU noise (csrc/riab_rates.hip noise_kernel) at one
+    step: one Philox4x32-7 call per (cell, group of 4 consecutive global agent ids), counter
+    (step, cell, agent_id0/4 + g, stream_tag(TAG_NOISE, pop_id)), key (seed lo, seed hi); two Box-Muller pairs, words
+    (x, y) -> agents 4g, 4g+1 and (z, w) -> agents 4g+2, 4g+3: radius uniform `((a >> 8) + 0.5) * 2^-24`, angle
+    uniform `(b >> 8) * 2^-24` in revolutions.  -> `(n_cells, n_agents)` float64.
+    The uniforms are the device's exact fp32 values (`(a >> 8) + 0.5` rounds to even in fp32 from 2^23 on: near
+    u = 1 the radius sqrt(-2 log u) is small and that rounding moves it by up to 2^-12); log / sqrt / cos / sin are
+    float64 here, the fp32 hardware approximations on the device (~1e-6 of z)."""
+    assert agent_id0 % 4 == 0 and n_agents % 4 == 0
+    g = (np.arange(n_agents // 4, dtype=np.uint64) + np.uint64(agent_id0 // 4))[None, :]
+    cell = np.arange(n_cells, dtype=np.uint64)[:, None]
+    x, y, z, w = philox4x32_10(step & 0xFFFFFFFF, cell, g, stream_tag(TAG_NOISE, pop_id),
+                               seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, rounds=SPIKE_ROUNDS)
+    def bm(a, b):
+        u_r = ((a >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0**-24)
+        u_a = (b >> np.uint32(8)).astype(np.float64) * 2.0**-24
+        r = np.sqrt(-2.0 * np.log(u_r.astype(np.float64)))
+        return r * np.cos(TWO_PI * u_a), r * np.sin(TWO_PI * u_a)
+    z0, z1 = bm(x, y)
+    z2, z3 = bm(z, w)
+    return np.stack((z0, z1, z2, z3), axis=-1).reshape(n_cells, n_agents)
+
+
+def ou_noise_path(z, theta_dt, sigma_dt, x0=0.0):
+    """Neurons.update's OU noise over the rows of `z` (T, ...): `x <- x - theta_dt*x + sigma_dt*z[t]` (ou_increment
+    with drift 0, theta_dt = dt/tau, sigma_dt = sqrt(2 std^2/(tau dt)) * dt), float64.  -> the T states after each
+    step, `(T, ...)`."""
+    z = np.asarray(z, dtype=np.float64)
+    x = np.broadcast_to(np.asarray(x0, dtype=np.float64), z.shape[1:]).copy()
+    out = np.empty_like(z)
+    for t in range(z.shape[0]):
+        x = x - theta_dt * x + sigma_dt * z[t]
+        out[t] = x
+    return out
 
 
 # --------------------------------------------------------------------------------------------------

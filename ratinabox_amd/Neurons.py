@@ -163,12 +163,17 @@ class Neurons:
                     setattr(pop, k, v.data_ptr() if torch.is_tensor(v) else v)
             if self.noise_std == 0:
                 self.__dict__["_pop_cache"] = (vals, (float(self.min_fr), float(self.max_fr)), pop)
-        if self.noise_std != 0:  # the OU parameters of update() (Neurons.py:153-168), fixed for the plan's dt
-            tau, dt = float(self.noise_coherence_time), float(self.Agent.dt)
+        if self.noise_std != 0:  # the OU parameters of update() (Neurons.py:153-168) at the agent's dt
             pop.noise_state = self._noise.data_ptr()
-            pop.noise_theta_dt = dt / tau
-            pop.noise_sigma_dt = float(np.sqrt((2 * float(self.noise_std) ** 2) / (tau * dt))) * dt
+            pop.noise_theta_dt, pop.noise_sigma_dt = self._noise_constants(self.Agent.dt)
         return pop
+
+    def _noise_constants(self, dt):
+        """(theta_dt, sigma_dt) of riab_neuron_noise for a step of `dt`: utils.ornstein_uhlenbeck (utils.py:361-368)
+        with theta = 1/noise_coherence_time, sigma = sqrt(2 noise_std^2 / (tau dt)), both multiplied by dt."""
+        tau, dt = float(self.noise_coherence_time), float(dt)
+        sigma = float(np.sqrt((2 * float(self.noise_std) ** 2) / (tau * dt)))
+        return dt / tau, sigma * dt
 
     def _plan_scratch(self, pop):
         """What a step plan needs of this population besides its tables (called once per plan, with the plan's
@@ -248,11 +253,10 @@ class Neurons:
                          B=self._Bp, rates=rates, spikes=io_spikes, u_in=u_t if not need_noise else None,
                          dt=float(Ag.dt), step0=Ag._step_index, from_f64=True)
         if need_noise:
-            tau = float(self.noise_coherence_time)
-            sigma = float(np.sqrt((2 * float(self.noise_std) ** 2) / (tau * Ag.dt)))
+            theta_dt, sigma_dt = self._noise_constants(Ag.dt)
             z_t = None if zn is None else self._as_rows(zn, torch.float32)
             rc = _L.lib.riab_neuron_noise(_L.ptr(self._noise), _L.ptr(rates), _L.ptr(z_t), int(self.n), self._Bp, 1,
-                                          float(Ag.dt / tau), float(sigma * Ag.dt), int(Ag.rng_seed),
+                                          theta_dt, sigma_dt, int(Ag.rng_seed),
                                           int(Ag._step_index), int(self.pop_id), int(Ag.agent_id0),
                                           _L.current_stream())
             _L.check(rc, "riab_neuron_noise")
@@ -437,11 +441,10 @@ class Neurons:
             hook(self, "end", tc)
         if noisy:
             # rates -> + OU noise (sequential over the chunk's rows) -> spikes on the noisy rates
-            tau = float(self.noise_coherence_time)
-            sigma = float(np.sqrt((2 * float(self.noise_std) ** 2) / (tau * dt)))
+            theta_dt, sigma_dt = self._noise_constants(dt)
             Ag = self.Agent
             rc = _L.lib.riab_neuron_noise(_L.ptr(self._noise), _L.ptr(fr), None, int(self.n), Bp, int(tc),
-                                          float(dt / tau), float(sigma * dt), int(Ag.rng_seed), int(step0 + 1),
+                                          theta_dt, sigma_dt, int(Ag.rng_seed), int(step0 + 1),
                                           int(self.pop_id), int(Ag.agent_id0), stream)
             _L.check(rc, "riab_neuron_noise")
             if sp is not None:
@@ -1570,11 +1573,10 @@ class FeedForwardLayer(Neurons):
         fr, sp = self._chunk_view(out, t0, tc)
         self._gemm(xs, tc, self._Bp, fr, None, stream)
         if self.noise_std != 0:
-            tau = float(self.noise_coherence_time)
-            sigma = float(np.sqrt((2 * float(self.noise_std) ** 2) / (tau * dt)))
+            theta_dt, sigma_dt = self._noise_constants(dt)
             Ag = self.Agent
             rc = _L.lib.riab_neuron_noise(_L.ptr(self._noise), _L.ptr(fr), None, int(self.n), self._Bp, int(tc),
-                                          float(dt / tau), float(sigma * dt), int(Ag.rng_seed), int(step0 + 1),
+                                          theta_dt, sigma_dt, int(Ag.rng_seed), int(step0 + 1),
                                           int(self.pop_id), int(Ag.agent_id0), stream)
             _L.check(rc, "riab_neuron_noise")
         if sp is not None:

@@ -194,6 +194,7 @@ PROTOTYPES = {
     "riab_plan_set_forced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "riab_plan_set_agent_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "riab_plan_add": (C.c_int, [C.c_void_p, C.POINTER(RiabPopulation)]),
+    "riab_plan_set_noise": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float]),
     "riab_plan_set_population_history": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     "riab_plan_rows_free": (C.c_int64, [C.c_void_p]),
     "riab_plan_step_index": (C.c_uint64, [C.c_void_p]),

@@ -511,7 +511,7 @@ int riab::launch_bvc(const RiabEnv* env, const RiabRateIO* io, const double* tes
   a.k0 = (uint32_t)io->seed;
   a.k1 = (uint32_t)(io->seed >> 32);
   a.step0 = (uint32_t)io->step0;
-  a.tag = RIAB_TAG_SPIKES | ((uint32_t)io->pop_id & 0xFFu);
+  a.tag = riab::stream_tag(RIAB_TAG_SPIKES, io->pop_id);
   a.agent_id0 = io->agent_id0;
   a.n = n;
   a.K = K;

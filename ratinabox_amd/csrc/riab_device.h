@@ -1,4 +1,4 @@
-// Device-side helpers shared by the gfx950 kernels: Philox4x32-10, vector
+// Device-side helpers shared by the gfx950 kernels: Philox4x32-10 / -7, vector
 // load/store wrappers, error codes.  CDNA4 only (wave64); no portability layer.
 #pragma once
 
@@ -13,6 +13,12 @@
 #define RIAB_MAX_RESAMPLES 64  // bound on the rejection loop of the resample boundary condition
 
 namespace riab {
+
+// The fourth counter word of a population's spike or noise stream: the tag's base XOR the population's index.  The
+// bases' low byte is zero, so pop_id < 256 gives the bits of the former `BASE | (pop_id & 0xFF)`; from 256 on every
+// population keeps a stream of its own (the masked form gave population 256 the draws of population 0).
+// oracle/riab_oracle.py: stream_tag restates it.
+__host__ __device__ __forceinline__ uint32_t stream_tag(uint32_t base, int32_t pop_id) { return base ^ (uint32_t)pop_id; }
 
 // riab_set_option's storage (defined in riab_rates.hip): plain ints, read per call
 extern int g_options[RIAB_OPT_COUNT];
@@ -53,10 +59,11 @@ __device__ __forceinline__ u32x4 philox4x32_r(uint32_t c0, uint32_t c1, uint32_t
 __device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
   return philox4x32_r<10>(c0, c1, c2, c3, k0, k1);
 }
-// The spike streams: Philox4x32-7 — the smallest round count the generator's authors found to pass BigCrush (SC'11, table
-// 2; 10 is their default with a safety margin).  One call per (cell, four agents) in the epilogue of kernels that are
+// The spike and neuron-noise streams: Philox4x32-7 — the smallest round count the generator's authors found to pass
+// BigCrush (SC'11, table 2; 10 is their default with a safety margin).  One call per (cell, four agents) in the epilogue of kernels that are
 // otherwise bound by their stores: at ten rounds the generator was two thirds of the epilogue's instructions and took a
-// PlaceCells kernel from 6.5 to 4.3 TB/s (round 6).  oracle/riab_oracle.py: spike_uniforms restates it.
+// PlaceCells kernel from 6.5 to 4.3 TB/s (round 6).  The OU noise of Neurons.update (noise_kernel, riab_rates.hip)
+// draws from it too.  oracle/riab_oracle.py: spike_uniforms and noise_normals restate them.
 __device__ __forceinline__ u32x4 philox4x32_spikes(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
   return philox4x32_r<7>(c0, c1, c2, c3, k0, k1);
 }

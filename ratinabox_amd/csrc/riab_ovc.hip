@@ -144,7 +144,7 @@ static int launch_ovc(const RiabEnv* env, const RiabRateIO* io, const float* obj
   a.rates = io->rates; a.spikes = io->spikes; a.u_in = io->u_in;
   a.dt = io->dt; a.fr_scale = io->max_fr - io->min_fr; a.fr_min = io->min_fr;
   a.k0 = (uint32_t)io->seed; a.k1 = (uint32_t)(io->seed >> 32); a.step0 = (uint32_t)io->step0;
-  a.tag = RIAB_TAG_SPIKES | ((uint32_t)io->pop_id & 0xFFu);
+  a.tag = riab::stream_tag(RIAB_TAG_SPIKES, io->pop_id);
   a.agent_id0 = io->agent_id0;
   a.n = n; a.M = n_objects;
   a.n_internal = (walls_occlude && env->n_walls > 4) ? env->n_walls - 4 : 0;

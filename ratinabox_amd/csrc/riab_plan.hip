@@ -356,6 +356,14 @@ extern "C" int riab_plan_add(RiabPlan* p, const RiabPopulation* pop) {
   return (int)p->pops.size() - 1;
 }
 
+// Neurons.update reads Agent.dt (Neurons.py:153-168): a step at a new dt takes the noisy populations' OU constants with it
+extern "C" int riab_plan_set_noise(RiabPlan* p, int32_t index, float theta_dt, float sigma_dt) {
+  if (!p || index < 0 || index >= (int)p->pops.size() || !p->pops[index].noise_state) return RIAB_EINVAL;
+  p->pops[index].noise_theta_dt = theta_dt;
+  p->pops[index].noise_sigma_dt = sigma_dt;
+  return RIAB_OK;
+}
+
 extern "C" int riab_plan_set_population_history(RiabPlan* p, int32_t index, float* rates_base, uint8_t* spikes_base,
                                                 int64_t capacity_rows) {
   if (!p || index < 0 || index >= (int)p->pops.size() || capacity_rows < 0) return RIAB_EINVAL;

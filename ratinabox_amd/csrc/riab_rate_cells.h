@@ -25,7 +25,7 @@ struct RateArgs {
   float dt, fr_scale, fr_min;
   uint32_t k0, k1;       // Philox key (seed)
   uint32_t step0;
-  uint32_t tag;          // RIAB_TAG_SPIKES | pop_id
+  uint32_t tag;          // stream_tag(RIAB_TAG_SPIKES, pop_id)
   uint32_t group0;       // agent_id0 / 4
   int32_t n;
   int32_t cells_per_block;

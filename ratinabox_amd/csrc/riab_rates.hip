@@ -234,31 +234,34 @@ __global__ __launch_bounds__(256) void noise_kernel(float* noise, float* rates, 
                                                     int64_t qrow, int T, float theta_dt, float sigma_dt, uint32_t k0,
                                                     uint32_t k1, uint32_t step0, uint32_t tag, uint32_t group0) {
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int c = blockIdx.y;
   if (q >= qrow) return;
-  const int64_t off = ((int64_t)c * qrow + q) * 4;
   const int64_t row = (int64_t)n * qrow * 4;  // elements between consecutive time rows
-  v4f x = ldv4(noise + off);
-  // the OU recurrence is sequential in time: one lane walks the T rows of its (cell, 4 agents)
-  for (int t = 0; t < T; ++t) {
-    v4f z;
-    if (z_in) {
-      z = ldv4(z_in + t * row + off);
-    } else {
-      const u32x4 w = philox4x32_spikes(step0 + (uint32_t)t, (uint32_t)c, group0 + (uint32_t)q, tag, k0, k1);
-      // two Box-Muller pairs in fp32
-      const float u0 = ((float)(w.x >> 8) + 0.5f) * 0x1.0p-24f, u1 = (float)(w.y >> 8) * 0x1.0p-24f;
-      const float u2 = ((float)(w.z >> 8) + 0.5f) * 0x1.0p-24f, u3 = (float)(w.w >> 8) * 0x1.0p-24f;
-      const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
-      z = v4f{r0 * __builtin_amdgcn_cosf(u1), r0 * __builtin_amdgcn_sinf(u1), r1 * __builtin_amdgcn_cosf(u3),
-              r1 * __builtin_amdgcn_sinf(u3)};
+  // (cells stride by gridDim.y: the launch caps the grid's y extent at 65535 like the other launches of this library,
+  // a population may have more cells)
+  for (int c = blockIdx.y; c < n; c += gridDim.y) {
+    const int64_t off = ((int64_t)c * qrow + q) * 4;
+    v4f x = ldv4(noise + off);
+    // the OU recurrence is sequential in time: one lane walks the T rows of its (cell, 4 agents)
+    for (int t = 0; t < T; ++t) {
+      v4f z;
+      if (z_in) {
+        z = ldv4(z_in + t * row + off);
+      } else {
+        const u32x4 w = philox4x32_spikes(step0 + (uint32_t)t, (uint32_t)c, group0 + (uint32_t)q, tag, k0, k1);
+        // two Box-Muller pairs in fp32 (the angle in revolutions: v_cos_f32 / v_sin_f32 take turns, not radians)
+        const float u0 = ((float)(w.x >> 8) + 0.5f) * 0x1.0p-24f, u1 = (float)(w.y >> 8) * 0x1.0p-24f;
+        const float u2 = ((float)(w.z >> 8) + 0.5f) * 0x1.0p-24f, u3 = (float)(w.w >> 8) * 0x1.0p-24f;
+        const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+        z = v4f{r0 * __builtin_amdgcn_cosf(u1), r0 * __builtin_amdgcn_sinf(u1), r1 * __builtin_amdgcn_cosf(u3),
+                r1 * __builtin_amdgcn_sinf(u3)};
+      }
+      // utils.ornstein_uhlenbeck with drift 0: dx = theta*(0 - x)*dt + sigma*(dt*z)
+      x = x + (-theta_dt) * x + sigma_dt * z;
+      const v4f r = ldv4(rates + t * row + off);
+      *reinterpret_cast<v4f*>(rates + t * row + off) = r + x;
     }
-    // utils.ornstein_uhlenbeck with drift 0: dx = theta*(0 - x)*dt + sigma*(dt*z)
-    x = x + (-theta_dt) * x + sigma_dt * z;
-    const v4f r = ldv4(rates + t * row + off);
-    *reinterpret_cast<v4f*>(rates + t * row + off) = r + x;
+    *reinterpret_cast<v4f*>(noise + off) = x;
   }
-  *reinterpret_cast<v4f*>(noise + off) = x;
 }
 
 // one float4 per thread, workgroups in address order: the store roofline of the chip (6.9 TB/s
@@ -516,7 +519,7 @@ static RateArgs make_args(const RiabRateIO* io, int n, dim3* grid) {
   a.k0 = (uint32_t)io->seed;
   a.k1 = (uint32_t)(io->seed >> 32);
   a.step0 = (uint32_t)io->step0;
-  a.tag = RIAB_TAG_SPIKES | ((uint32_t)io->pop_id & 0xFFu);
+  a.tag = riab::stream_tag(RIAB_TAG_SPIKES, io->pop_id);
   a.group0 = (uint32_t)(io->agent_id0 / 4);
   a.n = n;
   const int64_t pblocks = (a.nquads + 255) / 256;
@@ -749,7 +752,7 @@ int launch_rate_stream(const RiabEnv* env, const RiabPopulation* pop, const floa
   a.k0 = (uint32_t)seed;
   a.k1 = (uint32_t)(seed >> 32);
   a.step0 = (uint32_t)(step0 + 1);  // Neurons.update after the (step0 + t + 1)-th Agent.update
-  a.tag = RIAB_TAG_SPIKES | ((uint32_t)pop->io.pop_id & 0xFFu);
+  a.tag = riab::stream_tag(RIAB_TAG_SPIKES, pop->io.pop_id);
   a.group0 = (uint32_t)(agent_id0 / 4);
   a.n = pop->n;
   a.cells_per_block = 0;
@@ -941,10 +944,10 @@ extern "C" int riab_neuron_noise(float* noise, float* rates, const float* z_in, 
   if (!noise || !rates || n <= 0 || B <= 0 || T <= 0) return RIAB_EINVAL;
   if (B % 4 || agent_id0 % 4 || (((uintptr_t)noise | (uintptr_t)rates | (uintptr_t)z_in) & 15)) return RIAB_EALIGN;
   const int64_t qrow = B / 4;
-  dim3 grid((unsigned)((qrow + 255) / 256), (unsigned)n, 1);
+  dim3 grid((unsigned)((qrow + 255) / 256), (unsigned)(n < 65535 ? n : 65535), 1);
   hipLaunchKernelGGL(noise_kernel, grid, dim3(256), 0, (hipStream_t)stream, noise, rates, z_in, n, qrow, T, theta_dt,
                      sigma_dt, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step,
-                     RIAB_TAG_NOISE | ((uint32_t)pop_id & 0xFFu), (uint32_t)(agent_id0 / 4));
+                     riab::stream_tag(RIAB_TAG_NOISE, pop_id), (uint32_t)(agent_id0 / 4));
   return (int)hipGetLastError();
 }
 

@@ -63,7 +63,7 @@ struct Step1Pop {
   int32_t group0, n_groups;
   float fr_scale, fr_min;
   float p0, p1, p2;   // PlaceCells: scale, half_scale (periodic wrap), top_hat_w2; GridCells: f0, 1 / (1 - f0)
-  uint32_t tag;       // RIAB_TAG_SPIKES | pop_id
+  uint32_t tag;       // stream_tag(RIAB_TAG_SPIKES, pop_id)
 };
 struct Step1Pops {
   int32_t n_pops, total_groups;
@@ -1240,7 +1240,7 @@ static int step1_fill_pop(Step1Pop& q, const RiabEnv* env, const Step1PopRef& re
   q.fr_scale = pop->io.max_fr - pop->io.min_fr;
   q.fr_min = pop->io.min_fr;
   q.p0 = q.p1 = q.p2 = 0.0f;
-  q.tag = RIAB_TAG_SPIKES | ((uint32_t)pop->io.pop_id & 0xFFu);
+  q.tag = riab::stream_tag(RIAB_TAG_SPIKES, pop->io.pop_id);
   switch (pop->kind) {
     case RIAB_POP_PLACE: {
       int d;

@@ -10,8 +10,8 @@
 path uses; the Python mirrors (`history`, `firingrate`, `_times`) are brought up to date lazily by
 `sync()` (called automatically by the accessors).  Results are identical to the eager loop: same
 kernels, same arguments, same RNG counters.  Populations with `noise_std > 0` are covered (their OU
-parameters are fixed at the plan's dt), FeedForwardLayers too as long as their input layers are
-recorded before them (weights are read from the device copies made when the plan is built:
+parameters follow the dt of the step, as update() reads Agent.dt), FeedForwardLayers too as long as
+their input layers are recorded before them (weights are read from the device copies made when the plan is built:
 rebuild the plan after editing `inputs[...]["w"]`)."""
 import numpy as np
 import torch
@@ -176,7 +176,7 @@ class StepPlan:
             agent._plan.close()
         Bp = agent._Bp
         self._row_scratch = torch.empty((_L.HIST_ROWS, Bp), dtype=torch.float32, device=agent._device)
-        self._dt = agent.dt
+        self._dt = agent.dt      # the dt the noisy populations' OU constants in the plan were computed for
         self._drift_key = None
         self._drift_t = None
         env, self._walls = agent.Environment.device_tables(agent._device)
@@ -279,6 +279,15 @@ class StepPlan:
         return self
 
     # ---- stepping --------------------------------------------------------------------------------
+    def _set_noise_dt(self, dt):
+        """Neurons.update reads Agent.dt (Neurons.py:153-168): the OU constants of the noisy populations follow a step
+        at a new dt, as the spike rule does."""
+        for i, N in enumerate(self.neurons):
+            if N.noise_std != 0:
+                theta_dt, sigma_dt = N._noise_constants(dt)
+                _L.check(_L.lib.riab_plan_set_noise(self._h, i, theta_dt, sigma_dt), "riab_plan_set_noise")
+        self._dt = dt
+
     def step(self, n_steps=1, drift_velocity=None, drift_to_random_strength_ratio=1, dt=None):
         ag = self.agent
         if ag._plan is not self:
@@ -306,6 +315,8 @@ class StepPlan:
                 _L.check(_L.lib.riab_plan_set_motion(self._h, motion, _L.ptr(drift)), "riab_plan_set_motion")
                 self._drift_t, self._drift_key = drift, key
                 ag.dt = dt
+        if dt != self._dt:
+            self._set_noise_dt(dt)
         if n_steps > self._rows_open:
             if n_steps > self.capacity:
                 raise ValueError(f"n_steps {n_steps} exceeds the plan's chunk capacity {self.capacity}")

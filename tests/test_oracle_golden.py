@@ -167,6 +167,107 @@ def test_philox_known_answers():
     assert u.dtype == np.float32 and u.min() >= 0 and u.max() < 1 and abs(u.mean() - 0.5) < 0.01
 
 
+# ---- the OU noise stream of Neurons.update (noise_normals / ou_noise_path): the restatement's own laws ----
+NOISE_SEED = (0x9E3779B9 << 32) | 0x12345   # key words both nonzero
+
+
+def _corr(a, b):
+    a, b = np.ravel(a) - np.mean(a), np.ravel(b) - np.mean(b)
+    return float(np.dot(a, b) / np.sqrt(np.dot(a, a) * np.dot(b, b)))
+
+
+def test_stream_tags():
+    """Spike / noise stream tags: the base XOR pop_id — today's bits below 256, a stream of its own from 256 on."""
+    for base in (orc.TAG_SPIKES, orc.TAG_NOISE):
+        assert base & 0xFF == 0
+        assert [orc.stream_tag(base, p) for p in (0, 7, 255)] == [base | p for p in (0, 7, 255)]
+        assert len({orc.stream_tag(base, p) for p in range(4096)}) == 4096
+    assert not np.array_equal(orc.spike_uniforms(3, 5, 0, 2, 64), orc.spike_uniforms(3, 5, 256, 2, 64))
+    assert not np.array_equal(orc.noise_normals(3, 5, 0, 2, 64), orc.noise_normals(3, 5, 256, 2, 64))
+
+
+def test_noise_normals_are_standard_normal():
+    """>= 1e5 draws over cells, agents and steps: mean 0, std 1 within 5 standard errors, KS against N(0,1)."""
+    from scipy import stats
+    z = np.concatenate([orc.noise_normals(NOISE_SEED, (1 << 32) - 3 + t, 7, 16, 2048, agent_id0=1 << 20).ravel()
+                        for t in range(4)])   # (steps across the 2^32 wrap of the counter word)
+    N = z.size
+    assert N >= 100_000 and z.dtype == np.float64 and np.isfinite(z).all()
+    assert abs(z.mean()) < 5 / np.sqrt(N)
+    assert abs(z.std() - 1) < 5 * np.sqrt(0.5 / N)
+    assert stats.kstest(z, "norm").pvalue > 1e-3
+    # the four words of a Philox block feed four different agents: no pairwise dependence between them
+    q = z.reshape(-1, 4)
+    for i in range(4):
+        for j in range(i + 1, 4):
+            assert abs(_corr(q[:, i], q[:, j])) < 5 / np.sqrt(len(q)), (i, j)
+
+
+def test_noise_streams_are_uncorrelated():
+    """Different populations, different cells, and the spike stream of the same (step, cell, group): uncorrelated."""
+    n, B, step = 8, 8192, 77
+    lim = 5 / np.sqrt(n * B)
+    z = {p: orc.noise_normals(NOISE_SEED, step, p, n, B) for p in (0, 1, 7, 255, 256, 511)}
+    for a in z:
+        for b in z:
+            if a < b:
+                assert abs(_corr(z[a], z[b])) < lim, (a, b)
+    rows = z[0]
+    for c in range(1, n):
+        assert abs(_corr(rows[0], rows[c])) < 5 / np.sqrt(B), c
+    for p in (0, 7):
+        u = orc.spike_uniforms(NOISE_SEED, step, p, n, B)
+        assert abs(_corr(z[p], u)) < lim and abs(_corr(np.abs(z[p]), u)) < lim, p
+    # neighbouring steps of the same population
+    assert abs(_corr(rows, orc.noise_normals(NOISE_SEED, step + 1, 0, n, B))) < lim
+
+
+def test_noise_normals_depend_on_global_agent_id_only():
+    """Sharding: agents [512, 1024) drawn by a shard with agent_id0 = 512 are those of the whole run, bit for bit."""
+    whole = orc.noise_normals(NOISE_SEED, 9, 3, 5, 1024)
+    assert np.array_equal(orc.noise_normals(NOISE_SEED, 9, 3, 5, 512, agent_id0=512), whole[:, 512:])
+    assert np.array_equal(orc.noise_normals(NOISE_SEED, 9, 3, 5, 12, agent_id0=300), whole[:, 300:312])
+
+
+def test_ou_noise_path_is_ou_increment():
+    """ou_noise_path is the reference's utils.ornstein_uhlenbeck (ou_increment) with drift 0, step after step."""
+    rng = np.random.default_rng(1)
+    dt, std, tau = 0.013, 0.7, 0.21
+    z = rng.standard_normal((30, 5, 6))
+    theta_dt = dt / tau
+    sigma_dt = np.sqrt(2 * std**2 / (tau * dt)) * dt
+    x0 = rng.standard_normal((5, 6))
+    got = orc.ou_noise_path(z, theta_dt, sigma_dt, x0)
+    x = x0
+    for t in range(len(z)):
+        x = x + orc.ou_increment(x, dt, 0.0, std, tau, z[t])
+        np.testing.assert_allclose(got[t], x, rtol=1e-12, atol=1e-14)
+
+
+@pytest.mark.parametrize("ratio", [0.01, 0.1, 0.5])
+def test_ou_noise_law(ratio):
+    """The discrete OU process from 0 on the oracle's own normals: Var x_t = sigma_dt^2 (1 - a^2t) / (1 - a^2), a =
+    1 - dt/tau, whose limit is noise_std^2 * 2 / (2 - dt/tau); Cov(x_t, x_t+k) = a^k Var x_t (lag-k autocorrelation
+    a^k).  Each within 5 standard errors of its estimator."""
+    std, T, B = 0.8, 200, 40_000
+    tau = 0.2
+    dt = ratio * tau
+    theta_dt, sigma_dt = dt / tau, np.sqrt(2 * std**2 / (tau * dt)) * dt
+    a = 1 - theta_dt
+    z = np.stack([orc.noise_normals(NOISE_SEED, 1000 + t, 5, 1, B)[0] for t in range(T)])
+    x = orc.ou_noise_path(z, theta_dt, sigma_dt)
+    t = np.arange(1, T + 1)
+    var = sigma_dt**2 * (1 - a ** (2 * t)) / (1 - a**2)
+    np.testing.assert_allclose(sigma_dt**2 / (1 - a**2), std**2 * 2 / (2 - ratio), rtol=1e-12)
+    for i in (0, 9, 49, T - 1):
+        assert abs(np.mean(x[i] ** 2) / var[i] - 1) < 5 * np.sqrt(2 / B), i
+    for k in (1, 10):
+        i = T - 1 - k
+        beta = np.dot(x[i], x[i + k]) / np.dot(x[i], x[i])
+        se = np.sqrt((var[i + k] - a ** (2 * k) * var[i]) / (B * var[i]))
+        assert abs(beta - a**k) < 5 * se, (k, beta, a**k)
+
+
 @pytest.mark.parametrize("tag", ["div", "uni"])
 def test_field_of_view_bvcs(tag):
     """FieldOfViewBVCs (Neurons.py:1847-1888) = the egocentric BVC on a radial manifold."""
