@@ -15,6 +15,7 @@
 // throughput variant.
 #include <cstdlib>
 #include "riab_device.h"
+#include "riab_handover.h"
 
 // The same contraction rule wherever this header is compiled (riab_agent.hip; riab_plan.hip next to the task
 // kernel, which switches contraction off for its own code): the stand-alone and the fused launch must agree
@@ -315,22 +316,11 @@ struct Wall {  // staged in LDS
 // kernel (the same inlined functions on the same operands).
 //
 // PUB (with PC): the trajectory is consumed by a firing-rate kernel that runs CONCURRENTLY (riab_simulate_fused,
-// rate_kernel_gated / stream_gate_kernel in riab_rates.hip).  The helper wave then writes the history rows write-through (agent-scope
-// `sc1` stores: the consumer sits on other CUs / XCDs whose L2s are not coherent with this one), drains them
-// (`s_waitcnt vmcnt(0)`) and publishes "steps done" in ctrl[RIAB_CTRL_PROGRESS + workgroup] with one relaxed
-// agent-scope store per four-step block.  Values are bit-identical to the other variants.
+// rate_kernel_gated / stream_gate_kernel in riab_rates.hip).  The helper wave then writes the history rows write-through
+// (st_agent_v4f: the consumer sits on other CUs / XCDs whose L2s are not coherent with this one), drains them and
+// publishes "steps done" in ctrl[RIAB_CTRL_PROGRESS + workgroup] with one relaxed agent-scope store per four-step block
+// (riab_handover.h).  Values are bit-identical to the other variants.
 #define RIAB_Z_BATCH 16
-
-typedef __attribute__((address_space(1))) unsigned long long riab_gu64;
-typedef __attribute__((address_space(1))) uint32_t riab_gu32;
-// 16 bytes write-through (two 8-byte agent-scope relaxed stores = global_store_dwordx2 ... sc1)
-__device__ __forceinline__ void store_v4f_agent(void* p, v4f v) {
-  riab_gu64* g = (riab_gu64*)(uintptr_t)p;
-  const unsigned long long lo = ((unsigned long long)__float_as_uint(v.y) << 32) | __float_as_uint(v.x);
-  const unsigned long long hi = ((unsigned long long)__float_as_uint(v.w) << 32) | __float_as_uint(v.z);
-  __hip_atomic_store(g, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(g + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // the two standard normals of `step` for agent `aid` as floats; `pw` carries the Philox block that
 // serves an (even, odd) pair of steps
@@ -913,7 +903,7 @@ __device__ __forceinline__ void agent_step_body(const AgentArgs& a) {
       if (j < n2) {
         const v4f v = *reinterpret_cast<const v4f*>(&s_hist[buf][j >> 1][(j & 1) * 4][0] + hist_lds_lane);
         char* const gj = reinterpret_cast<char*>(g0 + (int64_t)((j >> 1) * RIAB_HIST_ROWS + (j & 1) * 4) * a.B);
-        if (PUB) store_v4f_agent(gj + hist_glb_lane, v);
+        if (PUB) st_agent_v4f(gj + hist_glb_lane, v);
         else *reinterpret_cast<v4f*>(gj + hist_glb_lane) = v;
       }
     }
@@ -949,10 +939,8 @@ __device__ __forceinline__ void agent_step_body(const AgentArgs& a) {
     };
     // PUB: rows of steps < n have left this wave write-through and been acknowledged: the consumer may read them
     auto publish = [&](int n) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0)
-        __hip_atomic_store((riab_gu32*)(uintptr_t)(a.ctrl + RIAB_CTRL_PROGRESS_WORD(blockIdx.x)), (uint32_t)a.step0 + (uint32_t)n,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      drain_stores();
+      if (lane == 0) st_agent(a.ctrl + RIAB_CTRL_PROGRESS_WORD(blockIdx.x), (uint32_t)a.step0 + (uint32_t)n);
     };
     // Short launches publish a block as soon as the stepping wave has been released for the next one (latency
     // matters, and the rate kernel has not saturated HBM for long); long ones one block later (see finish_block).
@@ -985,9 +973,8 @@ __device__ __forceinline__ void agent_step_body(const AgentArgs& a) {
       }
     };
     if (PUB && lane == 0) {  // this workgroup is resident; its progress word first goes back to "no row of this launch yet"
-      __hip_atomic_store((riab_gu32*)(uintptr_t)(a.ctrl + RIAB_CTRL_PROGRESS_WORD(blockIdx.x)), (uint32_t)a.step0, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      st_agent(a.ctrl + RIAB_CTRL_PROGRESS_WORD(blockIdx.x), (uint32_t)a.step0);
+      drain_stores();
       atomicAdd(a.ctrl + RIAB_CTRL_STARTED, 1u);
     }
     __syncthreads();  // (the table-staging barrier of the stepping wave)

@@ -16,6 +16,7 @@
 //            load), one fused exponent per term: exp2(-(a d - a mu)^2 + T[c][k]).
 #include <type_traits>
 #include "riab_device.h"
+#include "riab_handover.h"
 
 #ifndef RIAB_BVC_XCH_KB
 #define RIAB_BVC_XCH_KB 1  // pairs of rays per pass over the walls in a workgroup that exchanges its rays (see cast_rays)
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(512) void bvc_kernel(const BvcArgs a) {
   float* const xrow = publish ? a.xch + (int64_t)tile * a.Kp * 64 + lane : nullptr;
   auto put = [&](int k, float d) {
     s_d[k * 64 + lane] = d;
-    if (publish) __hip_atomic_store((__attribute__((address_space(1))) float*)(uintptr_t)(xrow + k * 64), d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (publish) st_agent(xrow + k * 64, d);
   };
   // rays without a partner (see below), `count` of them: table index 0 for t = 0, t + off otherwise
   auto cast_single = [&](int count, int off) {
@@ -288,16 +289,15 @@ __global__ __launch_bounds__(512) void bvc_kernel(const BvcArgs a) {
     // whole tile comes from the exchange rows (past L1).  Partners that do not show up in time (a device that does not
     // hold the whole grid at once): this workgroup casts every ray itself — the same values either way.
     cast_rays(std::integral_constant<int, RIAB_BVC_XCH_KB>{}, wave + 8 * part, 8 * nparts, true);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (this wave's rows have been acknowledged)
+    drain_stores();  // (this wave's rows have been acknowledged)
     __syncthreads();
     __shared__ int s_all_here;
     if (tid == 0) {
-      typedef __attribute__((address_space(1))) uint32_t gu32;
-      gu32* const cnt = (gu32*)(uintptr_t)(a.xch_count + tile);
-      __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      uint32_t* const cnt = a.xch_count + tile;
+      fetch_add_agent(cnt, 1u);
       int ok = 0;
       for (int spins = 0; spins < 256; ++spins) {  // (~0.3 us per poll)
-        if ((int32_t)(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - a.xch_target) >= 0) {
+        if ((int32_t)(ld_agent(cnt) - a.xch_target) >= 0) {
           ok = 1;
           break;
         }
@@ -309,12 +309,7 @@ __global__ __launch_bounds__(512) void bvc_kernel(const BvcArgs a) {
     if (s_all_here) {
       const float* const x = a.xch + (int64_t)tile * a.Kp * 64;
       for (int i = tid; i < K * 16; i += 512) {  // 16 bytes per thread and pass
-        typedef __attribute__((address_space(1))) unsigned long long gu64;
-        gu64* const g = (gu64*)(uintptr_t)(x + 4 * i);
-        const unsigned long long lo = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long hi = __hip_atomic_load(g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *reinterpret_cast<unsigned long long*>(s_d + 4 * i) = lo;
-        *reinterpret_cast<unsigned long long*>(s_d + 4 * i + 2) = hi;
+        *reinterpret_cast<v4f*>(s_d + 4 * i) = ld_agent_v4f(x + 4 * i);
       }
     } else {
       cast_rays(std::integral_constant<int, 4>{}, wave, 8, false);

@@ -76,16 +76,7 @@ __device__ __forceinline__ u32x4 philox4x32_spikes(uint32_t c0, uint32_t c1, uin
 // (the one-launch closed-loop step: 16.8 MB of rates in 1.5 us, then the next step) gains 12 % from WT (9.67 -> 8.50 us
 // per step); a kernel that streams for milliseconds (rate_kernel_gated, 1024 rows) loses 9 % to it (1.45 -> 1.32 G
 // agent-steps/s: the L2 no longer combines the lanes' quads into full lines ahead of the memory channel).
-#ifndef RIAB_WT_MODE
-#define RIAB_WT_MODE 3
-#endif
-#if RIAB_WT_MODE == 1
-#define RIAB_WT_BITS "sc1"
-#elif RIAB_WT_MODE == 2
-#define RIAB_WT_BITS "sc0 sc1"
-#else
 #define RIAB_WT_BITS "sc1 nt"
-#endif
 #define RIAB_STORE_NT 0
 #define RIAB_STORE_WT 1
 typedef float riab_v4f __attribute__((ext_vector_type(4)));

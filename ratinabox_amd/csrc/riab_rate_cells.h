@@ -4,6 +4,7 @@
 // (riab_rates.hip) and the one-launch closed-loop step (riab_step1.hip): the same inlined code on the same operands,
 // so a rate is the same bits whichever kernel evaluates it.
 #include "riab_device.h"
+#include "riab_handover.h"
 
 namespace riab {
 
@@ -36,17 +37,6 @@ struct PosQuad {
 };
 
 __device__ __forceinline__ v4f ldv4(const float* p) { return *reinterpret_cast<const v4f*>(p); }
-// 16 bytes another kernel has published write-through: two 8-byte relaxed agent-scope loads
-// (global_load_dwordx2 ... sc1: served by L2, never by this CU's L1)
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-typedef __attribute__((address_space(1))) uint32_t gu32;
-__device__ __forceinline__ v4f ldv4_agent(const float* p) {
-  gu64* g = (gu64*)(uintptr_t)p;
-  const unsigned long long lo = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned long long hi = __hip_atomic_load(g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return v4f{__uint_as_float((uint32_t)lo), __uint_as_float((uint32_t)(lo >> 32)), __uint_as_float((uint32_t)hi),
-             __uint_as_float((uint32_t)(hi >> 32))};
-}
 
 // finish_rate: per-position epilogue on the rate already scaled to [min_fr, max_fr].
 // Neurons.update returns zeros while the agent's position is NaN (reference Neurons.py:163-164)
@@ -103,7 +93,7 @@ struct PlaceCell {
     return Pos{ldv4(a.pos_x + off), ldv4(a.pos_y + off)};
   }
   __device__ __forceinline__ Pos load_agent(const RateArgs& a, int64_t off) const {  // rows another kernel is publishing
-    return Pos{ldv4_agent(a.pos_x + off), ldv4_agent(a.pos_y + off)};
+    return Pos{ld_agent_v4f(a.pos_x + off), ld_agent_v4f(a.pos_y + off)};
   }
   // (riab_step1.hip: the same workgroup has just computed these positions and hands them over in LDS)
   __device__ __forceinline__ Pos from_rows(v4f x, v4f y, v4f, v4f) const { return Pos{x, y}; }
@@ -196,7 +186,7 @@ struct GridCell {
     return Pos{ldv4(a.pos_x + off), ldv4(a.pos_y + off)};
   }
   __device__ __forceinline__ Pos load_agent(const RateArgs& a, int64_t off) const {
-    return Pos{ldv4_agent(a.pos_x + off), ldv4_agent(a.pos_y + off)};
+    return Pos{ld_agent_v4f(a.pos_x + off), ld_agent_v4f(a.pos_y + off)};
   }
   __device__ __forceinline__ Pos from_rows(v4f x, v4f y, v4f, v4f) const { return Pos{x, y}; }
   static constexpr bool NEEDS_HD = false;
@@ -247,7 +237,7 @@ struct HDCell {
   const double* vx64;  // MODE 1 at the agent: rows RIAB_S_VEL_X / _Y of the float64 state (T = 1), or NULL
   const double* vy64;
   __device__ __forceinline__ Pos load_agent(const RateArgs& a, int64_t off) const {
-    return from_dirs(ldv4_agent(a.hd_x + off), ldv4_agent(a.hd_y + off));
+    return from_dirs(ld_agent_v4f(a.hd_x + off), ld_agent_v4f(a.hd_y + off));
   }
   __device__ __forceinline__ Pos from_rows(v4f, v4f, v4f hx, v4f hy) const { return from_dirs(hx, hy); }
   static constexpr bool NEEDS_HD = true;

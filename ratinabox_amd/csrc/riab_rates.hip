@@ -23,6 +23,7 @@
 
 #include "riab_device.h"
 #include "riab_rate_cells.h"
+#include "riab_handover.h"
 // how the spike bytes of the open-loop kernels are stored (riab_device.h: store_stream)
 #ifndef RIAB_SPIKE_POLICY_GATED
 #define RIAB_SPIKE_POLICY_GATED RIAB_STORE_NT
@@ -289,7 +290,6 @@ __global__ __launch_bounds__(256) void fill_kernel(float* dst, int64_t n4, float
 // flight — whereas a wave of this kernel ENDS after its stores and the slot is refilled at once.  With the
 // PlaceCells arithmetic in front of every store the persistent form reached 5.5-5.8 TB/s in every item shape
 // (5.3 in the real kernel), the non-persistent one with a poll per wave 6.2-6.3 [MI355X].
-typedef __attribute__((address_space(1))) unsigned long long gu64;
 struct StreamArgs {
   uint32_t* ctrl;
   uint32_t step_base;     // (uint32) step0 of the launch: progress words are absolute step counts
@@ -305,7 +305,7 @@ struct StreamArgs {
 // with the second launch (a kernel's first launch in a process resolves its code object: tens of microseconds; a
 // descheduled thread), in which case the start is anywhere after that end.  Only the first is what the counter is for.
 __device__ __forceinline__ bool ended_just_now(const uint32_t* ctrl, uint32_t gap_ticks) {
-  const unsigned long long end = __hip_atomic_load((gu64*)(uintptr_t)(ctrl + RIAB_CTRL_TRAJ_STAMPS + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned long long end = ld_agent(reinterpret_cast<const uint64_t*>(ctrl + RIAB_CTRL_TRAJ_STAMPS + 2));
   const unsigned long long now = __builtin_amdgcn_s_memrealtime();
   return now >= end && now - end < (unsigned long long)gap_ticks;
 }
@@ -313,8 +313,7 @@ __device__ __forceinline__ bool ended_just_now(const uint32_t* ctrl, uint32_t ga
 __device__ __forceinline__ int stream_progress(const StreamArgs& s, uint32_t q, int lane) {
   int rel = 0x7fffffff;
   if (lane < 4) {
-    const uint32_t v = __hip_atomic_load((gu32*)(uintptr_t)(s.ctrl + RIAB_CTRL_PROGRESS + 32 * q + lane), __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t v = ld_agent(s.ctrl + RIAB_CTRL_PROGRESS + 32 * q + lane);
     rel = (int)(v - s.step_base);      // stale words of earlier launches are <= step_base
     rel = rel < 0 ? 0 : rel;
   }
@@ -326,12 +325,12 @@ __device__ __forceinline__ int stream_progress(const StreamArgs& s, uint32_t q, 
 __device__ __forceinline__ void stream_wait(const StreamArgs& s, uint32_t q, int t, int lane) {
   int known = stream_progress(s, q, lane);
   for (uint32_t spins = 0; known <= t; ++spins) {
-    const uint32_t ab = __hip_atomic_load((gu32*)(uintptr_t)(s.ctrl + RIAB_CTRL_ABORT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t ab = ld_agent(s.ctrl + RIAB_CTRL_ABORT);
     if (__builtin_amdgcn_readfirstlane((int)ab)) return;  // the pipeline was aborted: results are invalid anyway
     if (spins >= s.spin_limit) {
       if (lane == 0) {
         atomicAdd(s.ctrl + RIAB_CTRL_TIMEOUTS, 1u);
-        __hip_atomic_store((gu32*)(uintptr_t)(s.ctrl + RIAB_CTRL_ABORT), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        st_agent(s.ctrl + RIAB_CTRL_ABORT, 1u);
       }
       return;
     }
@@ -373,8 +372,7 @@ __global__ __launch_bounds__(64 * WAVES) void rate_kernel_gated(const RateArgs a
   // first / last ROW take part: 4096 device-scope atomics on two words, 86 instead of 60 us per launch.)
   const bool grid_first = t == 0 && blockIdx.x == 0 && blockIdx.y == 0 && wv == 0;
   if (s.stamps && grid_first && lane == 0)
-    __hip_atomic_store((gu64*)(uintptr_t)(s.ctrl + RIAB_CTRL_STAMPS), (unsigned long long)__builtin_amdgcn_s_memrealtime(),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    st_agent(reinterpret_cast<uint64_t*>(s.ctrl + RIAB_CTRL_STAMPS), (uint64_t)__builtin_amdgcn_s_memrealtime());
   // The two kernels are meant to run side by side.  When the grid's first wave finds EVERY row of the call published
   // already, the trajectory kernel had finished before the rate stage began — both streams on one hardware queue
   // (DESIGN.md 7): counted, the host warns (Agent.diagnostics["pipeline_serialised"]).
@@ -383,7 +381,7 @@ __global__ __launch_bounds__(64 * WAVES) void rate_kernel_gated(const RateArgs a
       atomicAdd(s.ctrl + RIAB_CTRL_SERIALISED, 1u);
   }
 #ifdef RIAB_PIPE_PROFILE  // (tools/pipe_profile.py: per time row, on the device's constant clock, u64 words behind the ctrl block)
-  gu64* const dbg = (gu64*)(uintptr_t)(s.ctrl + 2048);
+  riab_g64* const dbg = (riab_g64*)(uintptr_t)(s.ctrl + 2048);
   const bool first_wg = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
   if (first_wg) dbg[1 * 64 + t] = (unsigned long long)__builtin_amdgcn_s_memrealtime();   // the row's first workgroup runs
 #endif
@@ -416,15 +414,13 @@ __global__ __launch_bounds__(64 * WAVES) void rate_kernel_gated(const RateArgs a
   }
 #ifdef RIAB_PIPE_PROFILE
   if (c0 + CPB >= a.n && blockIdx.x + 1 == gridDim.x && (threadIdx.x & 255u) == 0) {  // the row's last workgroup is done
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    drain_stores();
     dbg[3 * 64 + t] = (unsigned long long)__builtin_amdgcn_s_memrealtime();
   }
 #endif
   if (s.stamps && t + 1 == gridDim.z && c0 + CPB >= a.n) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0)
-      __hip_atomic_fetch_max((gu64*)(uintptr_t)(s.ctrl + RIAB_CTRL_STAMPS + 2), (unsigned long long)__builtin_amdgcn_s_memrealtime(),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    drain_stores();
+    if (lane == 0) fetch_max_agent(reinterpret_cast<uint64_t*>(s.ctrl + RIAB_CTRL_STAMPS + 2), (uint64_t)__builtin_amdgcn_s_memrealtime());
   }
 }
 
@@ -442,13 +438,12 @@ __global__ __launch_bounds__(64) void stream_gate_kernel(uint32_t* ctrl, uint32_
                                                          uint32_t final_target, uint32_t serial_gap) {
   const int lane = threadIdx.x;
   for (uint32_t spins = 0;; ++spins) {
-    const uint32_t v = __hip_atomic_load((gu32*)(uintptr_t)(ctrl + RIAB_CTRL_STARTED), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t v = ld_agent(ctrl + RIAB_CTRL_STARTED);
     bool ok = (int32_t)(v - started_target) >= 0;
     bool all_done = ok && final_target != 0u && spins == 0u;
     if (ok) {
       for (uint32_t w = lane; w < n_traj; w += 64) {
-        const uint32_t p = __hip_atomic_load((gu32*)(uintptr_t)(ctrl + RIAB_CTRL_PROGRESS_WORD(w)), __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t p = ld_agent(ctrl + RIAB_CTRL_PROGRESS_WORD(w));
         ok = ok && (int32_t)(p - progress_target) >= 0;
         all_done = all_done && (int32_t)(p - final_target) >= 0;
       }
@@ -457,11 +452,11 @@ __global__ __launch_bounds__(64) void stream_gate_kernel(uint32_t* ctrl, uint32_
         ended_just_now(ctrl, serial_gap) && lane == 0)
       atomicAdd(ctrl + RIAB_CTRL_SERIALISED, 1u);
     if (__builtin_amdgcn_ballot_w64(!ok) == 0) return;
-    if (__hip_atomic_load((gu32*)(uintptr_t)(ctrl + RIAB_CTRL_ABORT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    if (ld_agent(ctrl + RIAB_CTRL_ABORT)) return;
     if (spins >= spin_limit) {
       if (lane == 0) {
         atomicAdd(ctrl + RIAB_CTRL_TIMEOUTS, 1u);
-        __hip_atomic_store((gu32*)(uintptr_t)(ctrl + RIAB_CTRL_ABORT), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        st_agent(ctrl + RIAB_CTRL_ABORT, 1u);
       }
       return;
     }
@@ -480,9 +475,9 @@ __global__ __launch_bounds__(64) void stream_gate_kernel(uint32_t* ctrl, uint32_
 // earlier replay of the same captured call — left in the control block.
 __global__ __launch_bounds__(64) void stream_open_kernel(uint32_t* ctrl, uint32_t n_traj, uint32_t step_base) {
   for (uint32_t w = threadIdx.x; w < n_traj; w += 64)
-    __hip_atomic_store((gu32*)(uintptr_t)(ctrl + RIAB_CTRL_PROGRESS_WORD(w)), step_base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    st_agent(ctrl + RIAB_CTRL_PROGRESS_WORD(w), step_base);
   if (threadIdx.x == 0)
-    __hip_atomic_store((gu32*)(uintptr_t)(ctrl + RIAB_CTRL_STARTED), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    st_agent(ctrl + RIAB_CTRL_STARTED, 0u);
 }
 
 // ---- host side ------------------------------------------------------------------------------

@@ -35,6 +35,7 @@
 #include <utility>
 #include "riab_agent_kernel.h"
 #include "riab_rate_cells.h"
+#include "riab_handover.h"
 #include "riab_task_world_kernel.h"  // (last: riab_task_kernel.h, which it includes, turns fp contraction off for its own code)
 
 namespace riab {
@@ -112,7 +113,6 @@ __global__ __launch_bounds__(64) void walls_prepare_kernel(const AgentArgs a, Wa
   if (threadIdx.x == 0) *reinterpret_cast<uint32_t*>(out + RIAB_MAX_WALLS) = k.box_fast ? 1u : 0u;
 }
 
-typedef __attribute__((address_space(1))) uint32_t s1_gu32;
 // A wait that gave up (one lane): counted, and the step it happened in remembered (first / last, as "agent steps taken
 // once the step is done") — the host recomputes the fused populations' rows of those steps from the history rows
 // (plan.py: settle_fused; what a give-up can leave wrong is rates only: the writer computes the state from its own
@@ -128,7 +128,6 @@ __device__ __forceinline__ void step1_note_timeout(const Step1Sync& sy, uint32_t
 // bookkeeping's stores and the episode table's atomic are meant to stay in flight.  Nothing in global memory is handed
 // over at these barriers.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-typedef __attribute__((address_space(1))) unsigned long long s1_gu64;
 
 // The rest of TaskEnvironment.step in the same launch (TASK = task_kernel's MODE: 1 step, | 2 the caller's `if terminal:
 // reset()`, | 4 the scripted action of the next step) — what the step plan's motion + task launch did behind the motion
@@ -187,18 +186,6 @@ struct Step1Task {
 #define RIAB_S1_STAMP(k)
 #define RIAB_S1_STAMP_H(k)
 #endif
-// timing experiments (tools/build_step1_variants.sh): bit 0 no motion step, bit 1 no rate stores, bit 2 no write-back
-#ifndef RIAB_S1_ABLATE
-#define RIAB_S1_ABLATE 0
-#endif
-// ... of the task modes: task_kernel MODE bits left out (1 the step's bookkeeping, 2 resets, 4 the next action), 8: the
-// workgroups y >= 1 do not wait for the writer's verdict
-#ifndef RIAB_S1_TASK_DROP
-#define RIAB_S1_TASK_DROP 0
-#endif
-#ifndef RIAB_S1_STORE
-#define RIAB_S1_STORE RIAB_STORE_WT
-#endif
 #ifndef RIAB_S1_FEW
 #define RIAB_S1_FEW 1  // a task's second pass over the quads a reset moved: s1_group_few (0: the whole pass again, stored by those quads)
 #endif
@@ -236,11 +223,9 @@ __device__ __forceinline__ void s1_group(const Cell& cell, const Step1Pops& ps, 
       v4f rr = cell.eval(p, P);
       rr = finish_rate(rr * q.fr_scale + q.fr_min, P);  // [0,1] -> [min_fr, max_fr]
       if (store) {
-        if (RIAB_S1_ABLATE & 2) {
-          if (rr.x == 123.0f) *reinterpret_cast<v4f*>(q.rates + off) = rr;
-        } else if (NT) store_stream<RIAB_S1_STORE>(q.rates + off, rr);
+        if (NT) store_stream<RIAB_STORE_WT>(q.rates + off, rr);
         else *reinterpret_cast<v4f*>(q.rates + off) = rr;
-        if (SPK && q.spikes) spike_store<false, RIAB_S1_STORE>(sa, rr, off, ps.step0, (uint32_t)(c0 + j), ps.quad0 + quad);  // (wave-uniform)
+        if (SPK && q.spikes) spike_store<false, RIAB_STORE_WT>(sa, rr, off, ps.step0, (uint32_t)(c0 + j), ps.quad0 + quad);  // (wave-uniform)
       }
       off += B;
     }
@@ -295,9 +280,9 @@ __device__ __forceinline__ void s1_group_few(const Cell& cell, const Step1Pops& 
     if (my_quad >= 0 && c < q.n) {
       const uint32_t quad = quad0 + (uint32_t)my_quad;
       const int64_t off = (int64_t)c * B + 4 * (int64_t)quad;
-      if (NT) store_stream<RIAB_S1_STORE>(q.rates + off, rr);
+      if (NT) store_stream<RIAB_STORE_WT>(q.rates + off, rr);
       else *reinterpret_cast<v4f*>(q.rates + off) = rr;
-      if (SPK && q.spikes) spike_store<false, RIAB_S1_STORE>(sa, rr, off, ps.step0, (uint32_t)c, ps.quad0 + quad);
+      if (SPK && q.spikes) spike_store<false, RIAB_STORE_WT>(sa, rr, off, ps.step0, (uint32_t)c, ps.quad0 + quad);
     }
   }
 }
@@ -432,7 +417,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
   double w_pad_start0 = 0.0;
   uint8_t w_terminal_prev = 0;
   if (TASK) {
-    if (tlive) tin = task_lane_load<RT & ~RIAB_S1_TASK_DROP>(tk.a, b);  // (TM, declared below)
+    if (tlive) tin = task_lane_load<RT>(tk.a, b);
     if (hlive && (RT & 1)) trin = load_rewards_in(tk.a, b);
     if (writer) task_stage_goals(tk.a, s_goals, tid, NT_);
     if (WT && writer) {  // the world's list as this step finds it, the lane's reward rows: one batch with the state
@@ -514,7 +499,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
   __syncthreads();
 #ifdef RIAB_STEP1_PROFILE
   if (prof_slot >= 0) {  // (the state must have arrived: its first use would otherwise be timed with the motion step)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    drain_stores();
     RIAB_S1_STAMP(1)
   }
 #endif
@@ -539,7 +524,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     const MotionDraw d = motion_normals(a.step0, true, aid, a.k0, a.k1, pw);
     s_z[0][tid & 255] = d.z_rot;
     s_z[1][tid & 255] = d.z_spd;
-  } else if (!(RIAB_S1_ABLATE & 1)) {
+  } else {
     const lds_cf64_ptr lds_g = (lds_cf64_ptr)s_g;
 #pragma unroll
     for (int w = 0; w < 4; ++w) K.w4[w] = s_w[w < K.nw ? w : 0];
@@ -573,15 +558,14 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
   tr.new_x = tr.new_y = nullptr;  // none stored by the lane's reset itself)
   tr.pos_x = tr.pos_y = nullptr;
   tr.hist_x = tr.hist_y = nullptr;
-  constexpr int TM = RT & ~RIAB_S1_TASK_DROP;
   if (RT && writer && !mover) {  // (wave-uniform) the helper waves' share of the lanes' books, see above
-    if (hlive && (TM & 1)) {
+    if (hlive && (RT & 1)) {
       const RewardsOut ro = rewards_step(tk.a, (lds_f64_ptr)s_goals, b, trin);
       s_rw_n[tid & 255] = ro.n_rw;
       s_rw_total[tid & 255] = ro.total;
     }
     lds_barrier();  // (writer) the reward caches are up to date
-    if (hlive && (TM & 2)) {
+    if (hlive && (RT & 2)) {
       const ResetDraw d = reset_draw(tk.a, tr, b);
       s_draw_xy[0][tid & 255] = d.x;
       s_draw_xy[1][tid & 255] = d.y;
@@ -591,7 +575,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     lds_barrier();  // (writer) the resets' draws are in LDS
     RIAB_S1_STAMP_H(14)
   }
-  if (mover && !(RIAB_S1_ABLATE & 1)) {
+  if (mover) {
     const lds_cf64_ptr lds_h = (lds_cf64_ptr)s_h;
     const double z_rot = (double)s_z[0][tid], z_spd = (double)s_z[1][tid];
     rot = ou_step<double>(rot, m.rot_theta_kw, m.rot_drift_kw, m.rot_sigma_kw, dt, z_rot);
@@ -641,11 +625,10 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     const uint32_t others = gridDim.y - 1u;  // (<= RIAB_STEP1_SYNC_MAX_Y - 1: one lane per word)
     uint32_t v = sy.epoch;
     if ((uint32_t)lane < others)
-      v = __hip_atomic_load((s1_gu32*)(uintptr_t)(sy.words + (int64_t)blockIdx.x * RIAB_STEP1_SYNC_STRIDE + 1 + lane), __ATOMIC_RELAXED,
-                            __HIP_MEMORY_SCOPE_AGENT);
+      v = ld_agent(sy.words + (int64_t)blockIdx.x * RIAB_STEP1_SYNC_STRIDE + 1 + lane);
     return v;
   };
-  const bool wb = writer && mover && !(RIAB_S1_ABLATE & 4);  // (wave-uniform)
+  const bool wb = writer && mover;  // (wave-uniform)
   uint32_t seen = sy.epoch;
   LaneMid tmid = {0, 0, false, false, {false, 0, 0.0, 0.0, 0.0}, 0};
   // a wait for the segment's other workgroups (their state / action loads have returned), bounded
@@ -666,18 +649,18 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
   // env.reset()`, decided here), bits 8.. = the length of the list the NEXT step finds; [1..4] that list, four entries
   // a word.  Posted by the writer workgroup that took the last ticket; read by every wave that needs it (lanes 0-4).
   auto world_verdict = [&](bool& stale) -> unsigned long long {  // -> lane l: entry l's value (lanes 0-4), once all are fresh
-    const s1_gu64* const mail64 = (const s1_gu64*)(uintptr_t)tk.mail;
-    unsigned long long e = (unsigned long long)sy.epoch << 32;
+    const uint64_t* const mail64 = reinterpret_cast<const uint64_t*>(tk.mail);
+    unsigned long long e = mail_word(sy.epoch, 0u);
     const bool polls = lane < 5;
-    if (polls) e = __hip_atomic_load((s1_gu64*)(mail64 + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (polls) e = ld_agent(mail64 + lane);
     stale = false;
-    for (uint32_t spins = 0; __builtin_amdgcn_ballot_w64((uint32_t)(e >> 32) != sy.epoch) != 0; ++spins) {
+    for (uint32_t spins = 0; __builtin_amdgcn_ballot_w64(!mail_fresh(e, sy.epoch)) != 0; ++spins) {
       if (spins >= sy.spin_limit) {
         stale = true;
         break;
       }
       __builtin_amdgcn_s_sleep(4);
-      if (polls) e = __hip_atomic_load((s1_gu64*)(mail64 + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (polls) e = ld_agent(mail64 + lane);
     }
     return e;
   };
@@ -696,7 +679,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     // ticket reads them.  A barrier does not wait for them — the compiler puts `lgkmcnt(0)` in front of it, a workgroup's
     // waves need no more of each other —: without this wait the last workgroup read, once in some millions of steps
     // beside a foreign load, a row that had not arrived yet; tools/task_world_soak.py found it)
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) (an asm statement with a memory clobber here costs one instantiation a stack frame)
+    drain_stores_nofence_asm();  // (an asm statement here costs one instantiation a stack frame)
     __syncthreads();
     if (tid == 0) s_world.last = atomicAdd(tk.ctl, 1) == (int)gridDim.x - 1;
     __syncthreads();
@@ -723,8 +706,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
         if (tid == 0) v = (uint32_t)s_world.next_agent | ((uint32_t)s_world.n << 8);
         else v = (uint32_t)s_world.list[4 * tid - 4] | ((uint32_t)s_world.list[4 * tid - 3] << 8) |
                  ((uint32_t)s_world.list[4 * tid - 2] << 16) | ((uint32_t)s_world.list[4 * tid - 1] << 24);
-        __hip_atomic_store((s1_gu64*)(uintptr_t)tk.mail + tid, ((unsigned long long)sy.epoch << 32) | v, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+        st_agent(reinterpret_cast<uint64_t*>(tk.mail) + tid, mail_word(sy.epoch, v));
       }
     }
     if (mover) {
@@ -779,11 +761,11 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     asm volatile("" : "+v"(seen));
     if (tlive) {
       const RewardsOut ro = {s_rw_n[tid], s_rw_total[tid]};
-      tmid = task_lane_goals<TM>(tk.a, b, (lds_f64_ptr)s_goals, tin, ro, qx, qy, tk.t_env, tk.reward_out, tk.terminal_out, tk.diag, probe);
+      tmid = task_lane_goals<RT>(tk.a, b, (lds_f64_ptr)s_goals, tin, ro, qx, qy, tk.t_env, tk.reward_out, tk.terminal_out, tk.diag, probe);
     }
     lds_barrier();  // (writer) the resets' draws are in LDS
     if (tlive)
-      task_lane_reset<TM>(tk.a, tr, b, tin, tmid, qx, qy, tk.t_env, tk.diag, [&]() {
+      task_lane_reset<RT>(tk.a, tr, b, tin, tmid, qx, qy, tk.t_env, tk.diag, [&]() {
         return ResetDraw{s_draw_xy[0][tid], s_draw_xy[1][tid], ((u128)s_draw_list[1][tid] << 64) | (u128)s_draw_list[0][tid]};
       });
     const bool moved = tlive && !(qx == mx && qy == my);  // (a reset that teleported the lane)
@@ -792,8 +774,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     // has to be ordered against another — or against the bookkeeping's stores and the episode table's atomic, which are
     // still in flight.  This wave's two verdict entries (the halves of its lane mask) are posted every step.
     const unsigned long long lanes = __builtin_amdgcn_ballot_w64(moved);
-    const unsigned long long tag = (unsigned long long)sy.epoch << 32;
-    s1_gu64* const mail64 = (s1_gu64*)(uintptr_t)(tk.mail + (int64_t)blockIdx.x * RIAB_STEP1_MAIL_STRIDE);
+    uint64_t* const mail64 = reinterpret_cast<uint64_t*>(tk.mail + (int64_t)blockIdx.x * RIAB_STEP1_MAIL_STRIDE);
     // this wave's six verdict entries, posted every step: the halves of its mask of moved lanes and — what the others
     // would otherwise come back for, one more round trip — the new positions of its first two movers (a wave has more
     // than two once in thousands of steps: the others' positions go to their per-agent entries)
@@ -804,19 +785,19 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     const uint32_t x1 = (uint32_t)__builtin_amdgcn_readlane(xb, i1), y1 = (uint32_t)__builtin_amdgcn_readlane(yb, i1);
     if (lane < 6) {
       const uint32_t v = lane == 0 ? (uint32_t)lanes : lane == 1 ? (uint32_t)(lanes >> 32) : lane == 2 ? x0 : lane == 3 ? y0 : lane == 4 ? x1 : y1;
-      __hip_atomic_store(mail64 + 8 * wave + lane, tag | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      st_agent(mail64 + 8 * wave + lane, mail_word(sy.epoch, v));
     }
     if (lanes3 && moved && lane != i0 && lane != i1) {
-      __hip_atomic_store(mail64 + 32 + tid, tag | (uint32_t)xb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(mail64 + 288 + tid, tag | (uint32_t)yb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      st_agent(mail64 + 32 + tid, mail_word(sy.epoch, (uint32_t)xb));
+      st_agent(mail64 + 288 + tid, mail_word(sy.epoch, (uint32_t)yb));
     }
     RIAB_S1_STAMP(7)
     // (the others know; now what only this lane's books need: the ended episode's row, the new episode's goals, the next
     // action — the helper waves work it out from the list and the position while this wave stores —, the rows back)
     if (tlive) {
-      task_lane_episode<TM>(tk.a, tr, b, tin, tmid, tk.t_env, tk.diag);
-      task_lane_newgoals<TM>(tk.a, tr, tin, tmid);
-      if (TM & 4) {
+      task_lane_episode<RT>(tk.a, tr, b, tin, tmid, tk.t_env, tk.diag);
+      task_lane_newgoals<RT>(tk.a, tr, tin, tmid);
+      if (RT & 4) {
         s_draw_list[0][tid] = (unsigned long long)tin.L.list;
         s_draw_list[1][tid] = (unsigned long long)(tin.L.list >> 64);
         s_fin_n[tid] = tin.L.n_goals;
@@ -825,14 +806,14 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
       }
     }
     RIAB_S1_STAMP(13)
-    if (TM & 4) lds_barrier();  // (writer) the lanes' lists and positions are in LDS
+    if (RT & 4) lds_barrier();  // (writer) the lanes' lists and positions are in LDS
     if (tlive) {
-      task_lane_store<TM>(tk.a, b, tin, tmid);
+      task_lane_store<RT>(tk.a, b, tin, tmid);
       px = qx;
       py = qy;
     }
     RIAB_S1_STAMP(15)
-  } else if (RT && (TM & 4) && writer) {
+  } else if ((RT & 4) && writer) {
     // ---- the helper waves' last share: the coming step's action of every lane (get_goal_vector, :1555-1584), into the
     // drift buffer — which every workgroup of the segment read at the top: behind the arrival words, like the state
     uint32_t hseen = arrivals();
@@ -897,8 +878,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     }
   }
   if (!writer && tid == 0)
-    __hip_atomic_store((s1_gu32*)(uintptr_t)(sy.words + (int64_t)blockIdx.x * RIAB_STEP1_SYNC_STRIDE + blockIdx.y), sy.epoch,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    st_agent(sy.words + (int64_t)blockIdx.x * RIAB_STEP1_SYNC_STRIDE + blockIdx.y, sy.epoch);
 
   if (wb && !TASK) seen = arrivals();
   auto write_back = [&]() {
@@ -973,7 +953,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
   RIAB_S1_STAMP(3)
 #ifdef RIAB_STEP1_PROFILE
   if (prof_slot >= 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    drain_stores();
     RIAB_S1_STAMP(4)
   }
 #endif
@@ -1008,21 +988,19 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
       rx.y = l1 ? nx[1] : rx.y; ry.y = l1 ? ny[1] : ry.y;
       rx.z = l2 ? nx[2] : rx.z; ry.z = l2 ? ny[2] : ry.z;
       rx.w = l3 ? nx[3] : rx.w; ry.w = l3 ? ny[3] : ry.w;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the values this wave stored a moment ago are in place)
+      drain_stores();  // (the values this wave stored a moment ago are in place)
       rates_pass(rx, ry, true);
     }
   }
-  if (RT && !writer && wave_needs_pos && !(RIAB_S1_TASK_DROP & 8)) {
+  if (RT && !writer && wave_needs_pos) {
     // ---- did a reset move one of the segment's agents?  The writer's 4 x 6 verdict entries of this launch: one round
     // trip (they are usually there by now) says that they are posted, which agents moved and where (almost all of) them went.
-    const s1_gu64* const mail64 = (const s1_gu64*)(uintptr_t)(tk.mail + (int64_t)blockIdx.x * RIAB_STEP1_MAIL_STRIDE);
-    auto peek = [&](int at) -> unsigned long long {
-      return __hip_atomic_load((s1_gu64*)(mail64 + at), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    const uint64_t* const mail64 = reinterpret_cast<const uint64_t*>(tk.mail + (int64_t)blockIdx.x * RIAB_STEP1_MAIL_STRIDE);
+    auto peek = [&](int at) -> unsigned long long { return ld_agent(mail64 + at); };
     // entry `at`, last seen as `e`, once it carries this launch's epoch (bounded); lanes that do not `want` it pass
     auto fresh = [&](int at, bool want, unsigned long long e) -> unsigned long long {
-      if (!want) e = (unsigned long long)sy.epoch << 32;
-      for (uint32_t spins = 0; __builtin_amdgcn_ballot_w64((uint32_t)(e >> 32) != sy.epoch) != 0; ++spins) {
+      if (!want) e = mail_word(sy.epoch, 0u);
+      for (uint32_t spins = 0; __builtin_amdgcn_ballot_w64(!mail_fresh(e, sy.epoch)) != 0; ++spins) {
         if (spins >= sy.spin_limit) break;
         __builtin_amdgcn_s_sleep(4);
         if (want) e = peek(at);
@@ -1031,7 +1009,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     };
     const bool polls = lane < 32 && (lane & 7) < 6;  // lane 8 w + l: entry l of the writer's mover wave w
     const unsigned long long verdict = fresh(lane & 31, polls, polls ? peek(lane & 31) : 0ull);
-    bool stale = __builtin_amdgcn_ballot_w64((uint32_t)(verdict >> 32) != sy.epoch) != 0;
+    bool stale = __builtin_amdgcn_ballot_w64(!mail_fresh(verdict, sy.epoch)) != 0;
     RIAB_S1_STAMP(7)
     // this lane's quad of agents 4 lane .. 4 lane + 3 of the segment: patched where the mail says an agent was moved
     v4f rx = *reinterpret_cast<const v4f*>(&s_row[0][4 * lane]), ry = *reinterpret_cast<const v4f*>(&s_row[1][4 * lane]);
@@ -1070,7 +1048,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
         bool waiting = false;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-          waiting = waiting || (((extra4 >> k) & 1u) && ((uint32_t)(ex[k] >> 32) != sy.epoch || (uint32_t)(ey[k] >> 32) != sy.epoch));
+          waiting = waiting || (((extra4 >> k) & 1u) && (!mail_fresh(ex[k], sy.epoch) || !mail_fresh(ey[k], sy.epoch)));
         if (__builtin_amdgcn_ballot_w64(waiting) == 0) break;
         if (spins >= sy.spin_limit) {
           stale = true;
@@ -1103,7 +1081,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
       // (... by lanes that take one cell and one moved quad each — usually there is one, seldom more than three — instead
       // of every lane running all its cells for a quad that did not move: the pass, and the wave's wait for the writer, are
       // the tail of the step's critical path)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the values this wave stored for those quads a moment ago are in place)
+      drain_stores();  // (the values this wave stored for those quads a moment ago are in place)
       if (RIAB_S1_FEW) rates_few(rx, ry, mine_moved);
       else rates_pass(rx, ry, mine_moved);
     }
@@ -1112,10 +1090,10 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
   }
   if (wb) write_back();
   // (the ended episodes' rows, last: their slots in the table were asked for a write-back ago)
-  if ((TM & 2) && tlive) episode_log_store(tr, b, tmid.rec, tk.t_env, tk.diag);
+  if ((RT & 2) && tlive) episode_log_store(tr, b, tmid.rec, tk.t_env, tk.diag);
 #ifdef RIAB_STEP1_PROFILE
   if (prof_slot >= 0 && writer) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    drain_stores();
     RIAB_S1_STAMP(6)
   }
 #endif

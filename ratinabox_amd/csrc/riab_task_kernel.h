@@ -23,6 +23,7 @@
 //     can be fused as well, runs the whole step as ONE kernel that deals the pieces below to different waves
 //     (step1_task_kernel, riab_step1.hip).
 #include "riab_device.h"
+#include "riab_handover.h"
 
 // The reward recursions are compared bit for bit with the reference's float64 python arithmetic:
 // no fused multiply-adds in this file.
@@ -437,7 +438,7 @@ __device__ __forceinline__ EpisodeRecord reset_lane_episode(const TaskArgs& a, c
         // folds the lanes' requests into one and waits for the answer on the spot — the round trip this split is for)
         uintptr_t counter = (uintptr_t)r.ep_count;
         asm volatile("" : "+v"(counter));
-        rec.slot = __hip_atomic_fetch_add((__attribute__((address_space(1))) int*)counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rec.slot = fetch_add_agent((int32_t*)counter, 1);
       }
     }
   }

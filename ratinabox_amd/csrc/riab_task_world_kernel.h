@@ -4,6 +4,7 @@
 // (riab_step1.hip), whose writer workgroups keep the world's books.
 #include "riab_task_kernel.h"   // (turns fp contraction off for its own code)
 #include "riab_task_world_logic.h"
+#include "riab_handover.h"
 
 #pragma clang fp contract(off)
 
@@ -13,28 +14,10 @@ namespace riab {
 
 // What phase A hands to phase B across workgroups — a candidate's "stands inside" mask, its place on the work list, the
 // survivors' sum of its rewards, the length of its reward cache — travels write-through and is read past the reader's
-// L1 (relaxed agent-scope accesses: global_store / global_load ... sc1), the writer having waited for its stores'
+// L1 (st_agent / ld_agent, riab_handover.h), the writer having waited for its stores'
 // acknowledgement before it takes its ticket.  Two __threadfence() — a write-back of the L2's dirty lines on one side, an
 // invalidation on the other, 3-7 us between them on this chip — used to stand where the ticket is taken; a quiet step
 // (no candidate: nothing to hand over but the counter) paid them all the same.
-__device__ __forceinline__ void st_agent(uint64_t* p, uint64_t v) {
-  __hip_atomic_store((__attribute__((address_space(1))) unsigned long long*)(uintptr_t)p, (unsigned long long)v, __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint64_t ld_agent(const uint64_t* p) {
-  return (uint64_t)__hip_atomic_load((__attribute__((address_space(1))) unsigned long long*)(uintptr_t)p, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_agent(int32_t* p, int32_t v) {
-  __hip_atomic_store((__attribute__((address_space(1))) int*)(uintptr_t)p, (int)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int32_t ld_agent(const int32_t* p) {
-  return (int32_t)__hip_atomic_load((__attribute__((address_space(1))) int*)(uintptr_t)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_agent(double* p, double v) { st_agent(reinterpret_cast<uint64_t*>(p), (uint64_t)__double_as_longlong(v)); }
-__device__ __forceinline__ double ld_agent(const double* p) {
-  return __longlong_as_double((long long)ld_agent(reinterpret_cast<const uint64_t*>(p)));
-}
 
 struct WorldShared {  // phase B's state, in LDS
   uint8_t list[RIAB_TASK_MAX_GOALS];
@@ -141,8 +124,7 @@ __device__ __forceinline__ void world_phase_a(const TaskArgs& a, lds_f64_ptr goa
   }
   // (the world's flag; phase B rewrites the column when it changes — from another workgroup, possibly behind another L2:
   // written through here, so that the rewrite, which comes after this store's acknowledgement, is what stays)
-  __hip_atomic_store((__attribute__((address_space(1))) uint8_t*)(uintptr_t)(terminal_out + b), terminal_prev, __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
+  st_agent(terminal_out + b, terminal_prev);
 }
 
 // ---- phase B, by the whole workgroup that took the last ticket: the step's check passes over the shared list, the
@@ -153,7 +135,7 @@ __device__ bool world_phase_b(const TaskArgs& a, lds_f64_ptr goals, WorldShared&
                               double pad_start0, uint8_t terminal_prev, double* reward_out, uint8_t* terminal_out,
                               const uint64_t* met, const int32_t* cand, int32_t* ctl, int32_t* diag) {
   const int tid = (int)threadIdx.x;
-  int n_cand = __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  int n_cand = ld_agent(ctl + 1);
   if (n_cand > a.B) n_cand = (int)a.B;
   if (tid == 0) S.n_awards = 0;
   const bool sequential = a.goalorder == RIAB_GOALORDER_SEQUENTIAL;

@@ -42,9 +42,6 @@
 
 namespace riab {
 
-#ifndef RIAB_T4_ABLATE
-#define RIAB_T4_ABLATE 0  // timing experiments only (tools/traj_probe.py): bits switch parts of the step off
-#endif
 #ifdef RIAB_T4_PROFILE  // timing experiments only: shader-clock stamps of workgroup 0's G and S waves into a.z_out
 #define T4_STAMP(k) do { if (blockIdx.x == 0 && t < 256) { const long long c_ = clock64(); if (lane == 0) ((long long*)a.z_out)[t * 8 + (k)] = c_; } } while (0)
 #else
@@ -105,7 +102,7 @@ __device__ __forceinline__ void t4_flush_hist(const AgentArgs& a, const float* s
     if (j < n2) {
       const v4f v = *reinterpret_cast<const v4f*>(s_hist + ((j >> 1) * RIAB_HIST_ROWS + (j & 1) * 4) * 64 + hist_lds_lane);
       char* const gj = reinterpret_cast<char*>(g0 + (int64_t)((j >> 1) * RIAB_HIST_ROWS + (j & 1) * 4) * a.B);
-      if (PUB) store_v4f_agent(gj + hist_glb_lane, v);
+      if (PUB) st_agent_v4f(gj + hist_glb_lane, v);
       else *reinterpret_cast<v4f*>(gj + hist_glb_lane) = v;
     }
   }
@@ -118,14 +115,14 @@ __device__ __forceinline__ void t4_flush_hist(const AgentArgs& a, const float* s
 // rate kernel, 3-4 us of the 11 us between that kernel's end and the return of a host synchronisation [MI355X]).
 template <bool PUB>
 __device__ __forceinline__ void t4_store_state(double* p, double v) {
-  if (PUB) __hip_atomic_store((riab_gu64*)(uintptr_t)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (PUB) st_agent(p, v);
   else *p = v;
 }
 // (PUB) this wave's state stores and counters have been acknowledged: tell the tail wave
 template <bool PUB>
 __device__ __forceinline__ void t4_state_stored(uint32_t* s_cnt, int lane) {
   if (PUB) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    drain_stores();
     if (lane == 0) __hip_atomic_fetch_add(&s_cnt[T4_C_STATE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
 }
@@ -208,7 +205,7 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
       RIAB_EXACT_FP
       constexpr bool OPEN = decltype(open_tag)::value;
       uint32_t noise_ready = 0, tail_done = 0;
-      const bool repel = K.nw > 0 && K.repel && !(RIAB_T4_ABLATE & 2);
+      const bool repel = K.nw > 0 && K.repel;
       for (int t = 0; t < T; ++t) {
         if ((uint32_t)t >= noise_ready) {
           noise_ready = t4_wait_counter(cnt, T4_C_NOISE, (uint32_t)t, false);
@@ -225,10 +222,8 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
         // ---- wall repulsion: everything that depends on the position only ----
         NearWalls<R> near = {INFINITY, 0, 0, 0, 0, 0, 0};
         WallPush<R> push = {0, 0, 0, 0};
-        if (!(RIAB_T4_ABLATE & 2)) {
-          if (OPEN) box_pass1<R>(K, px, py, near);
-          else near = walls_pass1<R>(K, s_w, px, py);
-        }
+        if (OPEN) box_pass1<R>(K, px, py, near);
+        else near = walls_pass1<R>(K, s_w, px, py);
         if (repel) {
           push = OPEN ? box_pass2_terms<R>(K, near) : walls_pass2_terms<R>(K, s_w, near, px, py);
           dwall = closest_wall_distance<R>(K, near);
@@ -245,7 +240,7 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
         if (repel) walls_pass2_apply<R>(K, push, px, py, vx, vy);
         // ---- propose (Agent.py:216), collisions ----
         propose_step<R>(vx, vy, dt, px, py);
-        if (!(RIAB_T4_ABLATE & 2)) handle_collisions<R>(K, s_w, near.x2min, ppx, ppy, px, py, vx, vy, n_bounce, n_sat);
+        handle_collisions<R>(K, s_w, near.x2min, ppx, ppy, px, py, vx, vy, n_bounce, n_sat);
         // the velocity of this step is final: wave S can start on the next one
         v2 = norm2(vx, vy);
         if (t + 1 < T) *slot_v2 = (unsigned long long)__double_as_longlong(v2);
@@ -260,7 +255,7 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
           dpx = px - ppx;
           dpy = py - ppy;
         } else {
-          if (!(RIAB_T4_ABLATE & 2)) boundary_net<R>(K, a, s_w, t, b, aid, px, py, n_bc, n_sat);
+          boundary_net<R>(K, a, s_w, t, b, aid, px, py, n_bc, n_sat);
           step_displacement<R>(a, px, py, ppx, ppy, dpx, dpy);
         }
         if ((uint32_t)t >= tail_done + RIAB_T4_RING) {  // the ring slot still holds a step wave T has not taken
@@ -310,10 +305,6 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
       const R z_spd = s_zs[t % RIAB_T4_RING][lane];
       // utils.rayleigh_to_normal / normal_to_rayleigh (utils.py:409-421), sigma = speed_mean: the expressions of
       // agent_step_body's float64 path
-      if (RIAB_T4_ABLATE & 1) {
-        *slot_f = (unsigned long long)__double_as_longlong(1.0 + 1e-9 * z_spd);
-        continue;
-      }
       if (v2 == (R)0) v2 = (R)1e-16;
       const R ispeed = r_rsqrt(v2);
       const R speed = v2 * ispeed;
@@ -359,9 +350,6 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
         }
         z_rot = (t & 3) == 0 ? zin[0][0] : (t & 3) == 1 ? zin[1][0] : (t & 3) == 2 ? zin[2][0] : zin[3][0];
         z_spd = (t & 3) == 0 ? zin[0][1] : (t & 3) == 1 ? zin[1][1] : (t & 3) == 2 ? zin[2][1] : zin[3][1];
-      } else if (RIAB_T4_ABLATE & 8) {
-        z_rot = 0.25;
-        z_spd = -0.5;
       } else {
         const MotionDraw d = motion_normals(a.step0 + (uint64_t)t, t == 0, aid, a.k0, a.k1, pw);
         pw = d.pw;
@@ -377,12 +365,7 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
       // utils.ornstein_uhlenbeck on the rotational velocity (Agent.py:287-294), then sin / cos of the heading increment
       rot = ou_step<R>(rot, (R)m.rot_theta_kw, (R)m.rot_drift_kw, (R)m.rot_sigma_kw, dt, z_rot);
       R sn, cs;
-      if (RIAB_T4_ABLATE & 8) {
-        sn = rot * dt;
-        cs = 1.0;
-      } else {
-        sincos_small(rot * dt, &sn, &cs);
-      }
+      sincos_small(rot * dt, &sn, &cs);
       s_cs[t % RIAB_T4_RING][lane] = cs;
       s_sn[t % RIAB_T4_RING][lane] = sn;
       s_zs[t % RIAB_T4_RING][lane] = z_spd;
@@ -405,12 +388,10 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
       // again) would otherwise let a consumer take the earlier run's count for its own.  Whoever has waited for the
       // announcement (the started gate) finds the word reset; launches that continue where the last one ended never
       // see a word above their own rows anyway.
-      __hip_atomic_store((riab_gu32*)(uintptr_t)(a.ctrl + RIAB_CTRL_PROGRESS_WORD(blockIdx.x)), (uint32_t)a.step0, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
+      st_agent(a.ctrl + RIAB_CTRL_PROGRESS_WORD(blockIdx.x), (uint32_t)a.step0);
       if (blockIdx.x == 0)   // (device clock at the start of the trajectory: RIAB_STREAMER_OPT_STEP_NS measures with it)
-        __hip_atomic_store((riab_gu64*)(uintptr_t)(a.ctrl + RIAB_CTRL_TRAJ_STAMPS), (unsigned long long)__builtin_amdgcn_s_memrealtime(),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        st_agent(reinterpret_cast<uint64_t*>(a.ctrl + RIAB_CTRL_TRAJ_STAMPS), (uint64_t)__builtin_amdgcn_s_memrealtime());
+      drain_stores();
       atomicAdd(a.ctrl + RIAB_CTRL_STARTED, 1u);
     }
     // PUB: rows of steps < n have left this wave write-through and been acknowledged: the consumer may read them
@@ -419,9 +400,7 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
       if (lane == 0 && (blockIdx.x == 0 || blockIdx.x + 1 == gridDim.x) && n <= 64)
         ((unsigned long long*)(a.ctrl + 2048))[(blockIdx.x == 0 ? 0 : 4) * 64 + n] = (unsigned long long)__builtin_amdgcn_s_memrealtime();
 #endif
-      if (lane == 0)
-        __hip_atomic_store((riab_gu32*)(uintptr_t)(a.ctrl + RIAB_CTRL_PROGRESS_WORD(blockIdx.x)), (uint32_t)a.step0 + (uint32_t)n,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (lane == 0) st_agent(a.ctrl + RIAB_CTRL_PROGRESS_WORD(blockIdx.x), (uint32_t)a.step0 + (uint32_t)n);
     };
     // Blocks of rows: the first four steps of a launch leave one by one (a consumer that is already waiting gets its
     // first row after one step, not four), then four steps per block (eight float4 row stores).  Short launches
@@ -444,8 +423,7 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
           }
         }
         const int r = t % RIAB_T4_RING;
-        if (!(RIAB_T4_ABLATE & 16))
-          tl = step_tail<R>(tl, s_dp[r][lane][0], s_dp[r][lane][1], tail_c, a.step0 + (uint64_t)t, aid, a.k0, a.k1);
+        tl = step_tail<R>(tl, s_dp[r][lane][0], s_dp[r][lane][1], tail_c, a.step0 + (uint64_t)t, aid, a.k0, a.k1);
         if (a.hist) {
           float* sh = &s_hist[i * RIAB_HIST_ROWS * 64 + lane];
           sh[0 * 64] = s_pp[r][lane][0];
@@ -463,11 +441,11 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
       cnt[T4_C_TDONE] = (uint32_t)(t0 + n);  // (the ring slots of this block have been read)
       if (PUB && !early_pub && pending >= 0) {
         // the previous block's rows were stored a whole block ago: acknowledged by now, the wait is free
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        drain_stores();
         publish(pending);
         pending = -1;
       }
-      if (a.hist && !(RIAB_T4_ABLATE & 4)) {
+      if (a.hist) {
         __builtin_amdgcn_wave_barrier();  // (LDS serves a wave's requests in order: the reads below see the writes)
         t4_flush_hist<PUB>(a, s_hist, lane, t0, n);
         __builtin_amdgcn_wave_barrier();
@@ -475,7 +453,7 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
       t0 += n;
       if (PUB && t0 < T) {   // (the launch's last publication follows the state, below)
         if (early_pub) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          drain_stores();
           publish(t0);
         } else {
           pending = t0;
@@ -497,9 +475,8 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
       // (device clock at the end of workgroup 0's work, stored BEFORE the wait below so that whoever sees the last
       // publication finds this launch's stamp, not the previous one's)
       if (lane == 0 && blockIdx.x == 0)
-        __hip_atomic_store((riab_gu64*)(uintptr_t)(a.ctrl + RIAB_CTRL_TRAJ_STAMPS + 2), (unsigned long long)__builtin_amdgcn_s_memrealtime(),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        st_agent(reinterpret_cast<uint64_t*>(a.ctrl + RIAB_CTRL_TRAJ_STAMPS + 2), (uint64_t)__builtin_amdgcn_s_memrealtime());
+      drain_stores();
       if (t4_wait_counter(cnt, T4_C_STATE, 1u, true)) publish(T);
       else gave_up = true;
     }
@@ -508,7 +485,7 @@ __global__ __launch_bounds__(256) void traj4_kernel(const AgentArgs a) {
     // report it like the consumers' timeouts (Agent.diagnostics["pipeline_timeouts"]; diag[1]: saturations)
     if (PUB) {
       atomicAdd(a.ctrl + RIAB_CTRL_TIMEOUTS, 1u);
-      __hip_atomic_store((riab_gu32*)(uintptr_t)(a.ctrl + RIAB_CTRL_ABORT), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      st_agent(a.ctrl + RIAB_CTRL_ABORT, 1u);
     }
     if (a.diag) atomicAdd(a.diag + 1, 1);
   }

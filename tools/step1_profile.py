@@ -1,6 +1,6 @@
 """Where a one-launch step (csrc/riab_step1.hip) spends its time, on the device's constant clock.
 
-Needs a library built with -DRIAB_STEP1_PROFILE (tools/build_variants.sh step1prof) loaded through RIAB_HIP_LIB:
+Needs a library built with -DRIAB_STEP1_PROFILE (tools/build_step1_variants.sh prof:-DRIAB_STEP1_PROFILE) loaded through RIAB_HIP_LIB:
 three workgroups of the grid stamp s_memrealtime at the phase boundaries of every step (the last step's stamps stay).
 Prints, per workgroup, microseconds since the first writer's entry."""
 import sys

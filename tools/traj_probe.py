@@ -1,6 +1,6 @@
 """The trajectory kernel alone (no rate stage): one riab_agent_step launch of T steps for 4096 agents in the open box,
-timed with events on the launch stream.  `RIAB_HIP_LIB=<variant .so>` selects a build (tools/build_variants.sh: the
-ablation builds of riab_traj4_kernel.h), RIAB_TRAJ2=1 the two-wave kernel of round 1."""
+timed with events on the launch stream.  `RIAB_HIP_LIB=<.so>` selects another build of the library (one compiled with
+other flags, e.g. -DRIAB_T4_PROFILE), RIAB_TRAJ2=1 the two-wave kernel of round 1."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,6 +1,6 @@
-"""Shader-clock profile of the four-wave trajectory kernel (a -DRIAB_T4_PROFILE build: tools/build_variants.sh prof):
-per step, for workgroup 0: G wave: loop top -> walls done -> f taken -> next |v|^2 sent -> step handed over; S wave:
-|v|^2 taken -> f sent.  RIAB_HIP_LIB=tools/exp/libt4_prof.so python tools/traj_profile.py"""
+"""Shader-clock profile of the four-wave trajectory kernel (a library built with -DRIAB_T4_PROFILE added to the
+flags of ratinabox_amd/_build.py): per step, for workgroup 0: G wave: loop top -> walls done -> f taken -> next |v|^2
+sent -> step handed over; S wave: |v|^2 taken -> f sent.  RIAB_HIP_LIB=<that .so> python tools/traj_profile.py"""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
