@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RIAB_ABI_VERSION 8
+#define RIAB_ABI_VERSION 9
 #define RIAB_MAX_WALLS 64     /* walls staged in LDS by the motion / BVC / line-of-sight kernels */
 #define RIAB_MAX_TEST_ANGLES 360
 #define RIAB_STATE_ROWS 12    /* rows of the agent state matrix, see below */
@@ -943,8 +943,65 @@ int riab_set_option(int32_t option, int32_t value);
  * active waiting; 0 restores the runtime's default.  Affects the current device of the calling thread. */
 int riab_host_wait_spin(int32_t on);
 
+/* ---- on-device TD(lambda) learning: contribs.ValueNeuron / contribs.SuccessorFeatures ------------------------------
+ * ONE learner fed by the whole batch: one weight matrix per input layer, per-lane value, derivative, TD error and
+ * eligibility traces; the weight change of a step is the MEAN over the B real lanes of the reference's per-agent
+ * outer product (B == 1: the reference's rule to the letter).  The constants of the learner: */
+typedef struct RiabTDParams {
+  float dt;      /* Agent.dt */
+  float tau;     /* discount time horizon (> 0) */
+  float tau_e;   /* eligibility-trace time scale (>= 0; 0: the trace IS the input rates) */
+  float eta;     /* learning rate */
+  float L2;      /* L2 regularisation */
+  int64_t B;     /* real lanes (agents) */
+  int64_t Bp;    /* padded lanes: the row length of every [rows][Bp] array, a multiple of 4 */
+  int32_t n;     /* value neurons */
+  int32_t Mp;    /* n rounded up to a multiple of 32 (row length of W^T) */
+} RiabTDParams;
+
+/* One input layer of the learner. */
+typedef struct RiabTDLayer {
+  const float* rates;  /* device float32 [n_in][Bp]: the input layer's rates of this step (phi) */
+  float* trace;        /* device float32 [n_in][Bp]: the eligibility trace, updated in place */
+  float* wt;           /* device float32 [n_in][Mp]: W^T as riab_feedforward reads it (RiabFFInput.wt), updated in place */
+  int32_t n_in;
+} RiabTDLayer;
+
+/* The tail of ValueNeuron.update() behind the parent's riab_feedforward (contribs/ValueNeuron.py:61-77):
+ *   dvdt = (v - v_last) / dt;  v_last = v                                  (ValueNeuron.py:61-66)
+ *   with_trace != 0:  trace_l = dt * rates_l + (1 - dt / tau_e) * trace_l  (ValueNeuron.py:68-76; tau_e == 0: trace_l =
+ *                     rates_l, the assignment the reference's branch intends)
+ * v, v_last, dvdt device float32 [n][Bp]; v or dvdt NULL skips the first part (the trace alone).  with_trace == 0
+ * leaves the traces to riab_td_update(fuse_trace = 1). */
+int riab_td_forward_tail(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers, const float* v,
+                         float* v_last, float* dvdt, int32_t with_trace, riab_stream_t stream);
+
+/* Floats of workspace riab_td_update needs for these shapes (the split-K partial sums); < 0: an argument error. */
+int64_t riab_td_workspace(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers);
+
+/* ValueNeuron.update_weights(reward) (contribs/ValueNeuron.py:79-101) for the whole batch:
+ *   td          = reward + dvdt - v / tau                                             (ValueNeuron.py:88-90)
+ *   W_l        += dt*eta*(1/B) * sum_{b<B} (td * prime)[:, b] (x) trace_l[:, b]  -  eta*dt*L2 * W_l   (:94-100)
+ * The contraction over the batch runs on the fp32 matrix cores, split over workgroups along the batch; the partial
+ * sums are added in a fixed order by a second launch (no float atomics: a run is bit-identical to the next).
+ * reward: device, float32 (reward_f64 == 0) or float64 (!= 0); element (i, b) is read at reward[i * reward_ld_n +
+ * b * reward_ld_b] for b < B only (strides in elements: 0, 0 a scalar; 1, 0 one per neuron; 0, 1 one per lane; Bp, 1 a
+ * full [n][Bp] array).  v, dvdt, prime device float32 [n][Bp]; td [n][Bp] is written.  Lanes b >= B contribute nothing,
+ * whatever they hold.  fuse_trace != 0: the trace update of riab_td_forward_tail is applied on the fly (the trace is
+ * read once per step, not twice).  workspace: riab_td_workspace() floats, 16-byte aligned. */
+int riab_td_update(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers, const void* reward,
+                   int32_t reward_f64, int64_t reward_ld_n, int64_t reward_ld_b, const float* v, const float* dvdt,
+                   const float* prime, float* td, int32_t fuse_trace, float* workspace, int64_t workspace_floats,
+                   riab_stream_t stream);
+
+/* ValueNeuron.reset() (contribs/ValueNeuron.py:103-113) for the lanes b < B with mask[b] != 0 (mask device uint8 [B];
+ * NULL: every lane): zeroes the columns of the traces and of the n_rows [n][Bp] arrays in `rows` (v, v_last, dvdt,
+ * td: at most 8). */
+int riab_td_reset(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers, float* const* rows,
+                  int32_t n_rows, const uint8_t* mask, riab_stream_t stream);
+
 /* sizeof of the ABI's structs as compiled into the library (which: 0 RiabEnv, 1 RiabMotion, 2 RiabRateIO,
- * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at
+ * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at
  * load */
 int64_t riab_abi_sizeof(int32_t which);
 

@@ -13,7 +13,7 @@ import torch  # noqa: F401
 
 from . import _build
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_WALLS = 64
 STATE_ROWS = 12
 HIST_ROWS = 8
@@ -53,6 +53,16 @@ class RiabRateIO(C.Structure):
 
 class RiabFFInput(C.Structure):
     _fields_ = [("rates", C.c_void_p), ("wt", C.c_void_p), ("n_in", C.c_int32)]
+
+
+class RiabTDParams(C.Structure):
+    """The constants of a TD learner (contribs.ValueNeuron): include/riab_hip.h RiabTDParams."""
+    _fields_ = [("dt", C.c_float), ("tau", C.c_float), ("tau_e", C.c_float), ("eta", C.c_float), ("L2", C.c_float),
+                ("B", C.c_int64), ("Bp", C.c_int64), ("n", C.c_int32), ("Mp", C.c_int32)]
+
+
+class RiabTDLayer(C.Structure):
+    _fields_ = [("rates", C.c_void_p), ("trace", C.c_void_p), ("wt", C.c_void_p), ("n_in", C.c_int32)]
 
 
 class RiabPopulation(C.Structure):
@@ -113,6 +123,7 @@ TW_TERMINAL, TW_GOAL_LIST, TW_ROWS = 7, 8, 24
 POP_KINDS = {"place": 0, "grid": 1, "hdc": 2, "bvc": 3, "ovc": 4, "ff": 5, "velocity": 6, "speed": 7, "random_spatial": 8}
 EINVAL = -1
 EALIGN = -2
+ETOOBIG = -3
 EFULL = -5
 EUNSUPPORTED = -4
 EPARTIAL = -6
@@ -186,6 +197,14 @@ PROTOTYPES = {
                                     C.c_uint64, C.c_uint64, C.c_int32, C.c_int64, C.c_void_p]),
     "riab_feedforward": (C.c_int, [C.POINTER(RiabFFInput), C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                    C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "riab_td_forward_tail": (C.c_int, [C.POINTER(RiabTDParams), C.POINTER(RiabTDLayer), C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_void_p]),
+    "riab_td_workspace": (C.c_int64, [C.POINTER(RiabTDParams), C.POINTER(RiabTDLayer), C.c_int32]),
+    "riab_td_update": (C.c_int, [C.POINTER(RiabTDParams), C.POINTER(RiabTDLayer), C.c_int32, C.c_void_p, C.c_int32,
+                                 C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                 C.c_void_p, C.c_int64, C.c_void_p]),
+    "riab_td_reset": (C.c_int, [C.POINTER(RiabTDParams), C.POINTER(RiabTDLayer), C.c_int32, C.POINTER(C.c_void_p),
+                                C.c_int32, C.c_void_p, C.c_void_p]),
     "riab_fill": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "riab_plan_create": (C.c_void_p, [C.POINTER(RiabEnv), C.POINTER(RiabMotion), C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
@@ -277,7 +296,7 @@ def _load():
     # the ctypes mirrors must have the layouts the library was compiled with (a stale library with the same
     # version number would otherwise corrupt memory silently)
     mirrors = ((0, RiabEnv), (1, RiabMotion), (2, RiabRateIO), (3, RiabPopulation), (4, RiabTask), (5, RiabFFInput),
-               (7, RiabSimulate), (8, RiabWatch))
+               (7, RiabSimulate), (8, RiabWatch), (9, RiabTDParams), (10, RiabTDLayer))
     for which, cls in mirrors:
         if lib.riab_abi_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"libriab_hip.so: sizeof({cls.__name__}) is {lib.riab_abi_sizeof(which)} in the library, "

@@ -923,6 +923,8 @@ extern "C" int64_t riab_abi_sizeof(int32_t which) {
     case 6: return (int64_t)RIAB_TS_ROWS;
     case 7: return (int64_t)sizeof(RiabSimulate);
     case 8: return (int64_t)sizeof(RiabWatch);
+    case 9: return (int64_t)sizeof(RiabTDParams);
+    case 10: return (int64_t)sizeof(RiabTDLayer);
     default: return -1;
   }
 }

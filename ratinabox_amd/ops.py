@@ -16,6 +16,8 @@ Functional operators (return a new tensor)
     spikes                                                              uint8 (T, n, B) from rates (T, n, B)
     feedforward                                                         float32 (T, n_out, B)
 In-place operators
+    td_forward_tail  the tail of ValueNeuron.update(): dV/dt, V_last and (optionally) the eligibility traces
+    td_update        ValueNeuron.update_weights(reward): TD error, batch-mean gradient on the matrix cores, W^T updated
     agent_step_      T fused Agent.update() steps on the float64 state (12, B); writes the history rows
     simulate_        T x (Agent.update(); N.update() for N in populations) as ONE native call (riab_simulate): the state,
                      the trajectory rows and every population's rate / spike rows are written
@@ -221,6 +223,105 @@ def feedforward(inputs: List[Tensor], weights_t: List[Tensor], bias: Tensor, act
     _L.check(_L.lib.riab_feedforward(arr, len(inputs), _L.ptr(bias), n_out, T, B, int(activation), pars, _L.ptr(out), None,
                                      _L.current_stream()), "riab_feedforward")
     return out
+
+
+# ---- TD learning: contribs.ValueNeuron / SuccessorFeatures -------------------------------------------------------
+def _td_structs(n: int, B: int, Bp: int, consts: List[float], rates: List[Tensor], traces: List[Tensor],
+                weights_t: List[Tensor]):
+    """(RiabTDParams, RiabTDLayer array) from operator arguments; consts = [dt, tau, tau_e, eta, L2]."""
+    if len(consts) != 5:
+        raise ValueError("consts must be [dt, tau, tau_e, eta, L2]")
+    if not rates or len(rates) != len(traces) or len(rates) != len(weights_t) or len(rates) > 8:
+        raise ValueError("1..8 input layers: one rates, one trace and one transposed weight tensor each")
+    p = _L.RiabTDParams()
+    p.dt, p.tau, p.tau_e, p.eta, p.L2 = (float(c) for c in consts)
+    p.B, p.Bp, p.n, p.Mp = int(B), int(Bp), int(n), (int(n) + 31) // 32 * 32
+    arr = (_L.RiabTDLayer * len(rates))()
+    for l, (x, e, w) in enumerate(zip(rates, traces, weights_t)):
+        for name, t in (("rates", x), ("traces", e)):
+            if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.shape[1] != Bp:
+                raise ValueError(f"{name}[{l}] must be a contiguous float32 tensor (n_in, Bp)")
+        if e.shape[0] != x.shape[0]:
+            raise ValueError("traces[l] must have the shape of rates[l]")
+        if w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (x.shape[0], p.Mp):
+            raise ValueError("weights_t[l] must be contiguous float32 (n_in_l, Mp), Mp = n rounded up to 32")
+        arr[l].rates, arr[l].trace, arr[l].wt, arr[l].n_in = x.data_ptr(), e.data_ptr(), w.data_ptr(), int(x.shape[0])
+    return p, arr
+
+
+def _td_rows(t: Tensor, n: int, Bp: int, what: str):
+    if t.dtype != torch.float32 or tuple(t.shape) != (n, Bp) or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 tensor ({n}, {Bp})")
+
+
+def td_workspace_floats(n: int, n_ins: List[int], Bp: int) -> int:
+    """Floats of workspace `td_update` needs for a learner of n neurons over input layers of n_ins cells and Bp lanes."""
+    p = _L.RiabTDParams()
+    p.n, p.Bp, p.B = int(n), int(Bp), int(Bp)
+    arr = (_L.RiabTDLayer * len(n_ins))()
+    for l, k in enumerate(n_ins):
+        arr[l].n_in = int(k)
+    need = int(_L.lib.riab_td_workspace(p, arr, len(n_ins)))
+    if need < 0:
+        raise _L.RiabError(f"riab_td_workspace failed with code {need}: {_L.strerror(need)}")
+    return need
+
+
+@_register("td_forward_tail(Tensor v, Tensor(a!) v_last, Tensor(b!) dvdt, Tensor[] rates, Tensor(c!)[] traces, "
+           "Tensor[] weights_t, float[] consts, int B, bool with_trace) -> ()",
+           lambda v, v_last, dvdt, rates, traces, weights_t, consts, B, with_trace: None)
+def td_forward_tail(v: Tensor, v_last: Tensor, dvdt: Tensor, rates: List[Tensor], traces: List[Tensor],
+                    weights_t: List[Tensor], consts: List[float], B: int, with_trace: bool) -> None:
+    """The tail of ValueNeuron.update() (riab_td_forward_tail), in place: dvdt = (v - v_last) / dt; v_last = v; with
+    `with_trace` traces_l = dt * rates_l + (1 - dt / tau_e) * traces_l.  v, v_last, dvdt float32 (n, Bp); rates_l,
+    traces_l float32 (n_in_l, Bp); weights_t_l float32 (n_in_l, Mp) (not touched); consts = [dt, tau, tau_e, eta, L2];
+    B the real lanes."""
+    n, Bp = int(v.shape[0]), int(v.shape[1])
+    for name, t in (("v", v), ("v_last", v_last), ("dvdt", dvdt)):
+        _td_rows(t, n, Bp, name)
+    p, arr = _td_structs(n, B, Bp, consts, rates, traces, weights_t)
+    _L.check(_L.lib.riab_td_forward_tail(p, arr, len(rates), _L.ptr(v), _L.ptr(v_last), _L.ptr(dvdt),
+                                         1 if with_trace else 0, _L.current_stream()), "riab_td_forward_tail")
+
+
+def _reward_strides(reward: Tensor, n: int, B: int, Bp: int):
+    """(stride over neurons, stride over lanes) in elements of a reward tensor: a scalar, (n,) one per neuron, (B..,) one
+    per lane, (n, B..) one per neuron and lane (B.. = B or the padded Bp) — read in place, whatever its strides.  A 1-D reward of length n == B > 1
+    is read the reference's way: one per neuron."""
+    if reward.dtype not in (torch.float32, torch.float64):
+        raise ValueError("reward must be float32 or float64")
+    if reward.dim() == 0 or reward.numel() == 1:
+        return 0, 0
+    if reward.dim() == 1:
+        if reward.shape[0] == n:
+            return int(reward.stride(0)), 0
+        if reward.shape[0] in (B, Bp):
+            return 0, int(reward.stride(0))
+    elif reward.dim() == 2 and reward.shape[0] == n and reward.shape[1] in (B, Bp):
+        return int(reward.stride(0)), int(reward.stride(1))
+    raise ValueError(f"reward must be a scalar, (n,) = ({n},), (B,) = ({B},) or (n, B), got {tuple(reward.shape)}")
+
+
+@_register("td_update(Tensor(a!)[] weights_t, Tensor(b!)[] traces, Tensor[] rates, Tensor reward, Tensor v, Tensor dvdt, "
+           "Tensor prime, Tensor(c!) td, Tensor(d!) workspace, float[] consts, int B, bool fuse_trace) -> ()",
+           lambda weights_t, traces, rates, reward, v, dvdt, prime, td, workspace, consts, B, fuse_trace: None)
+def td_update(weights_t: List[Tensor], traces: List[Tensor], rates: List[Tensor], reward: Tensor, v: Tensor, dvdt: Tensor,
+              prime: Tensor, td: Tensor, workspace: Tensor, consts: List[float], B: int, fuse_trace: bool) -> None:
+    """ValueNeuron.update_weights(reward) for the whole batch (riab_td_update), in place: td = reward + dvdt - v / tau;
+    weights_t_l += dt * eta / B * sum_{b<B} (td * prime)[:, b] (x) traces_l[:, b] - eta * dt * L2 * weights_t_l (as W^T,
+    float32 (n_in_l, Mp)).  With `fuse_trace` the trace update of `td_forward_tail` is applied on the fly.  reward:
+    float32 / float64, a scalar, (n,), (B,) or (n, B) (see _reward_strides).  workspace: float32, at least
+    `td_workspace_floats(n, [n_in_l], Bp)` elements.  Lanes b >= B contribute nothing."""
+    n, Bp = int(v.shape[0]), int(v.shape[1])
+    for name, t in (("v", v), ("dvdt", dvdt), ("prime", prime), ("td", td)):
+        _td_rows(t, n, Bp, name)
+    p, arr = _td_structs(n, B, Bp, consts, rates, traces, weights_t)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous float32 tensor")
+    ld_n, ld_b = _reward_strides(reward, n, int(B), Bp)
+    _L.check(_L.lib.riab_td_update(p, arr, len(rates), _L.ptr(reward), 1 if reward.dtype == torch.float64 else 0, ld_n, ld_b,
+                                   _L.ptr(v), _L.ptr(dvdt), _L.ptr(prime), _L.ptr(td), 1 if fuse_trace else 0,
+                                   _L.ptr(workspace), int(workspace.numel()), _L.current_stream()), "riab_td_update")
 
 
 # ---- Agent.update ----------------------------------------------------------------------------------------------

@@ -1,0 +1,216 @@
+"""No-GPU checks of the TD learners (contribs.ValueNeuron / SuccessorFeatures): the float64 restatement of the rule
+(tests/td_oracle.py) is pinned to the reference's record bit for bit, its batched form is checked by hand, and the C ABI
+and the class surface are checked the way tests/test_abi_cpu.py checks the rest."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from tests import golden_util as gu
+from tests import td_oracle as tdo
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "riab_hip.h")
+
+RUNS = [("td_value.npz", "relu_", "relu"), ("td_value.npz", "linear_", "linear"), ("td_successor.npz", "", "relu")]
+
+
+@pytest.fixture(scope="module")
+def L():
+    from ratinabox_amd import _lib
+    return _lib
+
+
+# ---- the oracle --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,prefix,act", RUNS)
+def test_oracle_reproduces_the_reference_bit_for_bit(name, prefix, act):
+    """Fed with the fixture's phi_t, r_t and w_0, the float64 restatement gives the reference's V, firingrate_prime,
+    td_error and trace at every step and w after T/2 and T steps, exactly — in its batched form at B = 1."""
+    g = gu.load(name)
+    thr = float(g["threshold"]) if prefix == "relu_" else 0.0
+    ref, got = tdo.reference_of(g, prefix), tdo.replay(g, prefix, act, thr)
+    assert len(g["phi"]) >= 600
+    for k in ("V", "prime", "td", "trace", "w_half", "w_T"):
+        np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
+
+
+def test_fixture_kink_condition():
+    """The relu run crosses its kink and stays clear of it (what lets firingrate_prime be compared exactly)."""
+    g = gu.load("td_value.npz")
+    o = tdo.TDOracle([g["w0"]], g["dt"], g["tau"], g["tau_e"], g["eta"], g["L2"], "relu", 1.0, float(g["threshold"]))
+    dist, zero = [], 0
+    for t in range(len(g["phi"])):
+        o.update([g["phi"][t]])
+        dist.append(np.abs(o.pre - float(g["threshold"])).min())
+        zero += int((o.V == 0).sum())
+        o.update_weights(g["r"][t])
+    assert min(dist) >= 1e-4
+    assert 0.01 <= zero / (2 * len(g["phi"])) <= 0.20
+
+
+def test_batched_oracle_is_the_mean_of_single_lane_updates():
+    rng = np.random.RandomState(5)
+    n, n_in, B = 3, 7, 3
+    w0 = rng.normal(size=(n, n_in)) * 0.3
+    kw = dict(dt=0.05, tau=1.5, tau_e=0.4, eta=0.02, L2=0.003, activation="relu", gain=1.2, threshold=0.05)
+    batch = tdo.TDOracle([w0], B=B, **kw)
+    for step in range(4):
+        phi, r = rng.uniform(size=(n_in, B)), rng.normal(size=(n, B))
+        singles = [tdo.TDOracle([batch.ws[0]], B=1, **kw) for _ in range(B)]
+        for b, s in enumerate(singles):   # a single lane carrying the batch's state of lane b
+            s.V, s.traces = batch.V[:, b:b + 1].copy(), [batch.traces[0][:, b:b + 1].copy()]
+        w_before = batch.ws[0].copy()
+        batch.update([phi])
+        batch.update_weights(r)
+        outer = []
+        for b, s in enumerate(singles):
+            s.update([phi[:, b]])
+            s.update_weights(r[:, b])
+            np.testing.assert_allclose(batch.V[:, b], s.V[:, 0], rtol=1e-13)
+            np.testing.assert_allclose(batch.td[:, b], s.td[:, 0], rtol=1e-12, atol=1e-14)
+            np.testing.assert_allclose(batch.traces[0][:, b], s.traces[0][:, 0], rtol=1e-13)
+            outer.append(np.outer(s.td[:, 0] * s.prime[:, 0], s.traces[0][:, 0]))
+        by_hand = w_before + kw["dt"] * kw["eta"] * (outer[0] + outer[1] + outer[2]) / 3 - kw["eta"] * kw["dt"] * kw["L2"] * w_before
+        np.testing.assert_allclose(batch.ws[0], by_hand, rtol=1e-12, atol=1e-15)
+    # a (B,) reward is one per lane, an (n,) reward one per neuron, a scalar both
+    a, b = tdo.TDOracle([w0], B=B, **kw), tdo.TDOracle([w0], B=B, **kw)
+    phi = rng.uniform(size=(n_in, B))
+    a.update([phi]); b.update([phi])
+    a.update_weights(0.7); b.update_weights(np.full((n, B), 0.7))
+    np.testing.assert_array_equal(a.ws[0], b.ws[0])
+    # reset of a subset of the lanes
+    a.reset(np.array([True, False, True]))
+    assert not a.traces[0][:, [0, 2]].any() and a.traces[0][:, 1].any() and not a.V[:, [0, 2]].any()
+
+
+# ---- the C ABI ---------------------------------------------------------------------------------------------------
+def test_td_symbols_are_exported_and_prototyped(L):
+    for s in ("riab_td_forward_tail", "riab_td_workspace", "riab_td_update", "riab_td_reset"):
+        assert hasattr(L.lib, s) and s in L.PROTOTYPES, s
+    assert L.ABI_VERSION >= 9 and L.lib.riab_abi_version() == L.ABI_VERSION
+
+
+def test_td_struct_layouts_match_header(L):
+    src = open(HEADER).read()
+    body = re.search(r"typedef struct RiabTDParams \{(.*?)\} RiabTDParams;", src, re.S).group(1)
+    fields = re.findall(r"^\s*(float|int64_t|int32_t)\s+(\w+);", body, re.M)
+    assert [f[1] for f in fields] == ["dt", "tau", "tau_e", "eta", "L2", "B", "Bp", "n", "Mp"]
+    assert [f[1] for f in fields] == [f[0] for f in L.RiabTDParams._fields_]
+    # natural C layout on LP64: five floats, padding to 8, two int64, two int32
+    P = L.RiabTDParams
+    assert (P.dt.offset, P.tau.offset, P.tau_e.offset, P.eta.offset, P.L2.offset) == (0, 4, 8, 12, 16)
+    assert (P.B.offset, P.Bp.offset, P.n.offset, P.Mp.offset) == (24, 32, 40, 44) and C.sizeof(P) == 48
+    Y = L.RiabTDLayer
+    assert (Y.rates.offset, Y.trace.offset, Y.wt.offset, Y.n_in.offset) == (0, 8, 16, 24) and C.sizeof(Y) == 32
+    assert L.lib.riab_abi_sizeof(9) == C.sizeof(P) and L.lib.riab_abi_sizeof(10) == C.sizeof(Y)
+
+
+def _learner(L, **over):
+    p = L.RiabTDParams()
+    p.dt, p.tau, p.tau_e, p.eta, p.L2, p.B, p.Bp, p.n, p.Mp = 0.05, 1.0, 0.25, 0.01, 0.001, 5, 8, 2, 32
+    for k, v in over.items():
+        setattr(p, k, v)
+    lay = (L.RiabTDLayer * 1)()
+    lay[0].rates = lay[0].trace = lay[0].wt = 16
+    lay[0].n_in = 8
+    return p, lay
+
+
+def test_td_argument_errors_before_launch(L):
+    """Negative codes come from validation only: no device needed."""
+    ok = C.c_void_p(16)
+    p, lay = _learner(L)
+    need = L.lib.riab_td_workspace(p, lay, 1)
+    assert need >= 2 * 8
+
+    def tail(p, lay, n_layers=1):
+        return L.lib.riab_td_forward_tail(p, lay, n_layers, ok, ok, ok, 1, None)
+
+    def update(p, lay, ws=ok, floats=1 << 30, v=ok):
+        return L.lib.riab_td_update(p, lay, 1, ok, 0, 0, 0, v, ok, ok, ok, 0, ws, floats, None)
+
+    rows = (C.c_void_p * 4)(16, 16, 16, 16)
+
+    def reset(p, lay, rows=rows, n=4):
+        return L.lib.riab_td_reset(p, lay, 1, rows, n, None, None)
+
+    for call in (tail, update, reset):
+        assert call(None, lay) == L.EINVAL and call(p, None) == L.EINVAL                       # null pointers
+        assert call(_learner(L, Bp=6)[0], lay) == L.EALIGN                                     # Bp % 4
+        assert call(_learner(L, tau_e=-0.1)[0], lay) == L.EINVAL                               # tau_e < 0
+        assert call(_learner(L, n=40)[0], lay) == L.EINVAL                                     # n > Mp
+        bad = _learner(L)[1]
+        bad[0].trace = None
+        assert call(p, bad) == L.EINVAL
+        bad[0].trace = 20
+        assert call(p, bad) == L.EALIGN                                                        # misaligned rows
+    assert tail(p, lay, 9) == L.ETOOBIG
+    assert update(p, lay, v=None) == L.EINVAL and update(p, lay, ws=None) == L.EINVAL
+    assert update(p, lay, floats=need - 1) == L.EINVAL                                         # workspace too small
+    assert L.lib.riab_td_update(p, lay, 1, None, 0, 0, 0, ok, ok, ok, ok, 0, ok, 1 << 30, None) == L.EINVAL
+    assert reset(p, lay, rows=None) == L.EINVAL and reset(p, lay, n=9) == L.ETOOBIG
+    assert L.lib.riab_td_workspace(None, lay, 1) == L.EINVAL
+
+
+# ---- the classes ---------------------------------------------------------------------------------------------------
+@pytest.fixture()
+def cpu_agent():
+    import ratinabox_amd as riab
+    np.random.seed(0)
+    ag = riab.Agent(riab.Environment({}), {"n_agents": 3, "device": "cpu"})
+    return riab, ag, riab.PlaceCells(ag, {"n": 16})
+
+
+def test_value_neuron_defaults_and_surface(cpu_agent):
+    riab, ag, pcs = cpu_agent
+    from ratinabox_amd.contribs.ValueNeuron import ValueNeuron
+    vn = ValueNeuron(ag, {"input_layers": [pcs]})
+    assert (vn.tau, vn.tau_e, vn.eta, vn.L2, vn.n) == (2, 0.5, 0.001, 0.001, 1)
+    assert vn.activation_function == {"activation": "relu"} and isinstance(vn, riab.FeedForwardLayer)
+    assert ValueNeuron.default_params["tau_e"] is None
+    assert ValueNeuron(ag, {"input_layers": [pcs], "tau": 1.0, "tau_e": 0.1}).tau_e == 0.1
+    e = vn.inputs[pcs.name]
+    w = e["w"]
+    assert w.shape == (1, 16) and w.dtype == np.float64
+    np.testing.assert_array_equal(w, e["w_init"].astype(np.float32).astype(np.float64))   # the device copy is fp32
+    e["w"] = np.full((1, 16), 0.25)
+    np.testing.assert_array_equal(vn.inputs[pcs.name]["w"], np.full((1, 16), 0.25))
+    assert e["eligibility_trace"].shape == (16, 3) and not e["eligibility_trace"].any()
+    assert vn.firingrate_deriv.shape == (1, 3) and vn.td_error.shape == (1, 3) and vn.firingrate_prime.shape == (1, 3)
+    one = riab.Agent(riab.Environment({}), {"device": "cpu"})
+    v1 = ValueNeuron(one, {"input_layers": [riab.PlaceCells(one, {"n": 5})], "n": 2})
+    assert v1.td_error.shape == (2,) and list(v1.inputs.values())[0]["eligibility_trace"].shape == (5,)
+
+
+def test_successor_features_surface(cpu_agent):
+    riab, ag, pcs = cpu_agent
+    from ratinabox_amd.contribs.SuccessorFeatures import SuccessorFeatures
+    feats = riab.PlaceCells(ag, {"n": 6})
+    sf = SuccessorFeatures(ag, {"input_layers": [pcs], "features": feats, "n": 99})
+    assert sf.n == feats.n == 6 and sf.inputs[pcs.name]["w"].shape == (6, 16)
+    with pytest.raises(Exception, match="features"):
+        SuccessorFeatures(ag, {"input_layers": [pcs]})
+
+
+def test_refusals(cpu_agent):
+    riab, ag, pcs = cpu_agent
+    from ratinabox_amd.contribs.ValueNeuron import ValueNeuron
+    vn = ValueNeuron(ag, {"input_layers": [pcs]})
+    with pytest.raises(NotImplementedError, match="recurrent"):
+        vn.add_input(vn, recurrent=True)
+    with pytest.raises(NotImplementedError, match="recurrent"):
+        vn.add_input(pcs, recurrent=True)
+    with pytest.raises(NotImplementedError):
+        ValueNeuron(ag, {"input_layers": [pcs], "activation_function": lambda x, deriv=False: x})
+    assert vn.learning
+    with pytest.raises(NotImplementedError, match="step plan"):       # what a StepPlan / the AutoStepper asks of a population
+        vn._population({pcs: 0})
+    with pytest.raises(NotImplementedError, match="simulate"):        # what Agent.simulate() asks of it
+        vn._rates_from_trajectory(None, None, 0, 1, 0, 0.01, None)
+    vn.learning = False
+    assert vn._population({pcs: 0}).n == 1                              # frozen: a FeedForwardLayer like any other
+    shard = riab.Agent(riab.Environment({}), {"n_agents": 4, "device": "cpu", "agent_id0": 8})
+    with pytest.raises(NotImplementedError, match="shard"):
+        ValueNeuron(shard, {"input_layers": [riab.PlaceCells(shard, {"n": 4})]})
