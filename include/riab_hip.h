@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RIAB_ABI_VERSION 9
+#define RIAB_ABI_VERSION 10
 #define RIAB_MAX_WALLS 64     /* walls staged in LDS by the motion / BVC / line-of-sight kernels */
 #define RIAB_MAX_TEST_ANGLES 360
 #define RIAB_STATE_ROWS 12    /* rows of the agent state matrix, see below */
@@ -280,6 +280,23 @@ int riab_head_direction_cells(const RiabRateIO* io, const float* table, int32_t 
 int riab_velocity_cells(const RiabRateIO* io, const float* table, int32_t n, float one_sigma_speed,
                         const double* vel_x, const double* vel_y, riab_stream_t stream);
 
+/* contribs.PhasePrecessingPlaceCells.get_state at the agent (contribs/PhasePrecessingPlaceCells.py:66-119): the
+ * PlaceCells rate — the same code as riab_place_cells, the same bits —, scaled to [min_fr, max_fr] and THEN multiplied by
+ * a von Mises of the theta phase whose preferred phase precesses with the position along the direction of motion:
+ *   dir = v / (1e-8 + |v|), s = ((pos - centre) . dir) / sig_b, D / 2 pi = 0.5 - s * precess_fraction / 2 - theta_rev,
+ *   rate *= exp(kappa (cos D - 1)) * exp(kappa) / I0(kappa)
+ * (sig_b = width, twice the width for gaussian cells; no periodic wrap in pos - centre; a resting agent has dir = 0).
+ *  cells      device float32 [n][4] = (centre x, centre y, -log2(e) / (2 w^2), precess_fraction / (2 sig_b))
+ *  kappa      von Mises concentration (>= 0); exp(kappa) / I0(kappa) is worked out on the host in float64
+ *  theta_rev  theta phase of the row in revolutions: theta_freq * (Agent.t mod 1 / theta_freq)
+ *  vel_x / vel_y  device float64 [B], rows RIAB_S_VEL_X / _Y of the agent state (Agent.velocity, not the measured
+ *             velocity; 32-byte aligned; required: io->T must be 1)
+ * description: gaussian, gaussian_threshold, diff_of_gaussians or top_hat (RIAB_EINVAL otherwise); geometry: euclidean,
+ * solid or periodic room (line_of_sight / geodesic: RIAB_EUNSUPPORTED). */
+int riab_phase_precessing_place_cells(const RiabEnv* env, const RiabRateIO* io, const float* cells, int32_t n,
+                                      int32_t description, int32_t geometry, float top_hat_width, double kappa,
+                                      double theta_rev, const double* vel_x, const double* vel_y, riab_stream_t stream);
+
 /* SpeedCell.get_state (Neurons.py:2632-2651): one cell, |v| / one_sigma_speed scaled to
  * [min_fr, max_fr]; v = the float32 rows io->hd_x / hd_y (the newest history["vel"] = measured
  * velocity at the agent: rows RIAB_H_VEL_X / _Y).  rates is [T][1][B]. */
@@ -389,7 +406,7 @@ int riab_feedforward(const RiabFFInput* inputs, int32_t n_inputs, const float* b
  * row cursors, RNG counters and pointers are kept in C++, every kernel of every step is enqueued on
  * `stream`, nothing is allocated or synchronised. */
 enum { RIAB_POP_PLACE = 0, RIAB_POP_GRID = 1, RIAB_POP_HDC = 2, RIAB_POP_BVC = 3, RIAB_POP_OVC = 4, RIAB_POP_FF = 5,
-       RIAB_POP_VELOCITY = 6, RIAB_POP_SPEED = 7, RIAB_POP_RANDOM_SPATIAL = 8 };
+       RIAB_POP_VELOCITY = 6, RIAB_POP_SPEED = 7, RIAB_POP_RANDOM_SPATIAL = 8, RIAB_POP_THETA_PLACE = 9 };
 #define RIAB_FF_MAX_INPUTS 8
 
 typedef struct RiabPopulation {
@@ -438,6 +455,11 @@ typedef struct RiabPopulation {
   int32_t activation;        /* RIAB_ACT_* */
   float act_params[4];
   float* rates_prime;        /* device float32 [n][B] activation derivative, or NULL */
+  /* RIAB_POP_THETA_PLACE (riab_phase_precessing_place_cells): `table` is its [n][4] table, which carries the
+   * precess fraction; description / geometry / top_hat_width as for place.  The phase of a step is taken from the
+   * plan's clock (riab_plan_set_clock) */
+  double theta_freq;         /* Hz */
+  double kappa;
 } RiabPopulation;
 
 typedef struct RiabPlan RiabPlan;
@@ -459,6 +481,10 @@ int riab_plan_add(RiabPlan* plan, const RiabPopulation* pop);  /* returns the po
 int riab_plan_set_noise(RiabPlan* plan, int32_t index, float theta_dt, float sigma_dt);
 int riab_plan_set_population_history(RiabPlan* plan, int32_t index, float* rates_base, uint8_t* spikes_base,
                                      int64_t capacity_rows);
+/* Agent.t: the plan keeps it as a float64 clock advanced by `t += dt` (dt of the step's motion) once per agent step —
+ * the operation the per-step loop performs on Agent.t, so a step's theta phase is the same bits either way. */
+int riab_plan_set_clock(RiabPlan* plan, double t);
+double riab_plan_clock(const RiabPlan* plan);
 int64_t riab_plan_rows_free(const RiabPlan* plan);
 uint64_t riab_plan_step_index(const RiabPlan* plan);
 /* n_steps x (Agent.update(); every population's update()); RIAB_EFULL (nothing launched) when a

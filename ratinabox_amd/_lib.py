@@ -13,7 +13,7 @@ import torch  # noqa: F401
 
 from . import _build
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_WALLS = 64
 STATE_ROWS = 12
 HIST_ROWS = 8
@@ -78,7 +78,7 @@ class RiabPopulation(C.Structure):
                 ("noise_state", C.c_void_p), ("noise_theta_dt", C.c_float), ("noise_sigma_dt", C.c_float),
                 ("n_inputs", C.c_int32), ("input_index", C.c_int32 * 8), ("input_wt", C.c_void_p * 8),
                 ("bias", C.c_void_p), ("activation", C.c_int32), ("act_params", C.c_float * 4),
-                ("rates_prime", C.c_void_p)]
+                ("rates_prime", C.c_void_p), ("theta_freq", C.c_double), ("kappa", C.c_double)]
 
 
 class RiabSimulate(C.Structure):
@@ -120,7 +120,8 @@ TD_REWARD_OVERFLOW, TD_LATE_COMPLETIONS, TD_EPLOG_OVERFLOW, TD_RESETS = range(4)
 TW_N_GOALS, TW_DELAYED, TW_PAD_START, TW_EPISODE, TW_EP_START, TW_EP_ANY_ENDED, TW_STARTED = range(7)
 TW_TERMINAL, TW_GOAL_LIST, TW_ROWS = 7, 8, 24
 
-POP_KINDS = {"place": 0, "grid": 1, "hdc": 2, "bvc": 3, "ovc": 4, "ff": 5, "velocity": 6, "speed": 7, "random_spatial": 8}
+POP_KINDS = {"place": 0, "grid": 1, "hdc": 2, "bvc": 3, "ovc": 4, "ff": 5, "velocity": 6, "speed": 7, "random_spatial": 8,
+             "theta_place": 9}
 EINVAL = -1
 EALIGN = -2
 ETOOBIG = -3
@@ -183,6 +184,9 @@ PROTOTYPES = {
                                           C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "riab_velocity_cells": (C.c_int, [C.POINTER(RiabRateIO), C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "riab_phase_precessing_place_cells": (C.c_int, [C.POINTER(RiabEnv), C.POINTER(RiabRateIO), C.c_void_p, C.c_int32,
+                                                    C.c_int32, C.c_int32, C.c_float, C.c_double, C.c_double, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
     "riab_speed_cell": (C.c_int, [C.POINTER(RiabRateIO), C.c_float, C.c_void_p]),
     "riab_boundary_vector_cells": (C.c_int, [C.POINTER(RiabEnv), C.POINTER(RiabRateIO), C.c_void_p, C.c_void_p, C.c_int32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
@@ -215,6 +219,8 @@ PROTOTYPES = {
     "riab_plan_add": (C.c_int, [C.c_void_p, C.POINTER(RiabPopulation)]),
     "riab_plan_set_noise": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float]),
     "riab_plan_set_population_history": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
+    "riab_plan_set_clock": (C.c_int, [C.c_void_p, C.c_double]),
+    "riab_plan_clock": (C.c_double, [C.c_void_p]),
     "riab_plan_rows_free": (C.c_int64, [C.c_void_p]),
     "riab_plan_step_index": (C.c_uint64, [C.c_void_p]),
     "riab_plan_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

@@ -1,1 +1,9 @@
-"""Contributed layers on top of the hot path (mirrors the reference's `ratinabox.contribs`)."""
+"""Contributed layers on top of the hot path (mirrors the reference's `ratinabox.contribs`): one module per class, imported
+the reference's way —
+
+    from ratinabox_amd.contribs.TaskEnvironment import TaskEnvironment
+    from ratinabox_amd.contribs.ValueNeuron import ValueNeuron
+    from ratinabox_amd.contribs.SuccessorFeatures import SuccessorFeatures
+    from ratinabox_amd.contribs.PhasePrecessingPlaceCells import PhasePrecessingPlaceCells
+"""
+__all__ = ["TaskEnvironment", "ValueNeuron", "SuccessorFeatures", "PhasePrecessingPlaceCells"]

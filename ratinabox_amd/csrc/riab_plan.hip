@@ -56,6 +56,10 @@ struct RiabPlan {
   int64_t agent_id0;
   uint64_t seed;
   uint64_t step;  // number of Agent.update() steps taken so far (the RNG counter)
+  // Agent.t (riab_plan_set_clock): `clock` is the agent's time after `clock_step` updates; brought up to `step` by one
+  // `clock += motion.dt` per step taken since (plan_clock), the operation the per-step loop performs on Agent.t
+  double clock;
+  uint64_t clock_step;
   const double* drift;
   // imported / forced trajectory (riab_plan_set_forced): positions of the coming steps, [rows][2][B]; null = motion model
   const double* forced;
@@ -105,6 +109,11 @@ struct RiabPlan {
 };
 
 static int fused_agent_step(RiabPlan* p, float* row, hipStream_t s, bool need_free_row, uint32_t* mask, bool query);
+
+static double plan_clock(RiabPlan* p) {
+  for (; p->clock_step < p->step; ++p->clock_step) p->clock += p->motion.dt;
+  return p->clock;
+}
 
 // this step's rows of the plan's fused populations (split: those whose chunk has a free row); returns how many
 static int fused_refs(const RiabPlan* p, riab::Step1PopRef* refs, uint32_t* mask, bool need_free_row) {
@@ -254,6 +263,8 @@ extern "C" RiabPlan* riab_plan_create(const RiabEnv* env, const RiabMotion* moti
   p->agent_id0 = agent_id0;
   p->seed = seed;
   p->step = step;
+  p->clock = 0.0;
+  p->clock_step = step;
   p->drift = nullptr;
   p->forced = nullptr;
   p->forced_rows = p->forced_fill = 0;
@@ -315,6 +326,7 @@ extern "C" void riab_plan_destroy(RiabPlan* p) { delete p; }
 extern "C" int riab_plan_set_motion(RiabPlan* p, const RiabMotion* motion, const double* drift) {
   if (!p || !motion) return RIAB_EINVAL;
   if (motion->has_drift && !drift) return RIAB_EINVAL;
+  plan_clock(p);  // (the steps taken so far advanced the clock by the dt they were taken at)
   if (motion->wall_repel_distance_kw != p->motion.wall_repel_distance_kw) p->walls_ready = false;  // (the box fast path's verdict depends on it)
   p->motion = *motion;
   p->drift = drift;
@@ -342,7 +354,8 @@ extern "C" int riab_plan_set_agent_history(RiabPlan* p, float* hist_base, int64_
 }
 
 extern "C" int riab_plan_add(RiabPlan* p, const RiabPopulation* pop) {
-  if (!p || !pop || pop->n <= 0 || pop->kind < RIAB_POP_PLACE || pop->kind > RIAB_POP_RANDOM_SPATIAL) return RIAB_EINVAL;
+  if (!p || !pop || pop->n <= 0 || pop->kind < RIAB_POP_PLACE || pop->kind > RIAB_POP_THETA_PLACE) return RIAB_EINVAL;
+  if (pop->kind == RIAB_POP_THETA_PLACE && (!pop->table || !(pop->theta_freq > 0.0) || !(pop->kappa >= 0.0))) return RIAB_EINVAL;
   if (pop->kind == RIAB_POP_FF) {
     if (pop->n_inputs <= 0 || pop->n_inputs > RIAB_FF_MAX_INPUTS || !pop->bias) return RIAB_EINVAL;
     for (int l = 0; l < pop->n_inputs; ++l)  // feed-forward only: an input must already be in the plan
@@ -430,6 +443,15 @@ extern "C" int riab_plan_set_task_world(RiabPlan* p, double* world, uint64_t* me
 
 extern "C" double riab_plan_task_clock(const RiabPlan* p) { return p && p->has_task ? p->t_env : 0.0; }
 
+extern "C" int riab_plan_set_clock(RiabPlan* p, double t) {
+  if (!p || !(t == t)) return RIAB_EINVAL;
+  p->clock = t;
+  p->clock_step = p->step;
+  return RIAB_OK;
+}
+
+extern "C" double riab_plan_clock(const RiabPlan* p) { return p ? plan_clock(const_cast<RiabPlan*>(p)) : 0.0; }
+
 extern "C" int64_t riab_plan_rows_free(const RiabPlan* p) {
   if (!p) return 0;
   int64_t free_rows = p->hist_base ? p->hist_cap - p->hist_fill : INT64_MAX;
@@ -480,6 +502,13 @@ static int launch_population(RiabPlan* p, size_t i, const float* row, hipStream_
       rc = riab_velocity_cells(&io, q.table, q.n, q.one_sigma_speed, p->state + RIAB_S_VEL_X * B,
                                p->state + RIAB_S_VEL_Y * B, s);
       break;
+    case RIAB_POP_THETA_PLACE: {  // Agent.velocity and Agent.t: the float64 state rows and the plan's clock
+      const double period = 1.0 / q.theta_freq;
+      rc = riab_phase_precessing_place_cells(&p->env, &io, q.table, q.n, q.description, q.geometry, q.top_hat_width, q.kappa,
+                                             q.theta_freq * fmod(plan_clock(p), period), p->state + RIAB_S_VEL_X * B,
+                                             p->state + RIAB_S_VEL_Y * B, s);
+      break;
+    }
     case RIAB_POP_SPEED:  // history["vel"][-1]: the measured velocity of the step just taken
       io.hd_x = row + RIAB_H_VEL_X * B;
       io.hd_y = row + RIAB_H_VEL_Y * B;

@@ -50,6 +50,11 @@ __device__ __forceinline__ v4f finish_rate(v4f r, const PosQuad& P) {
 template <class P_>
 __device__ __forceinline__ v4f finish_rate(v4f r, const P_&) { return r; }
 
+// post_scale: per-(cell, position) factor on the rate already scaled to [min_fr, max_fr], in front of finish_rate
+// (rate_kernel_wide / rate_kernel_generic).  Nothing for every functor but ThetaPlaceCell.
+template <class Cell>
+__device__ __forceinline__ v4f post_scale(const Cell&, const float*, const typename Cell::Pos&, v4f r) { return r; }
+
 // ---- spike epilogue: Neurons.save_to_history (reference Neurons.py:681-687) -------------
 template <bool EXPLICIT_U, int POLICY = RIAB_STORE_NT>
 __device__ __forceinline__ void spike_store(const RateArgs& a, v4f r, int64_t off, uint32_t step, uint32_t c,
@@ -172,6 +177,66 @@ struct PlaceCell {
     return c;
   }
 };
+
+// ---- contribs.PhasePrecessingPlaceCells (reference contribs/PhasePrecessingPlaceCells.py:66-119) ----------
+// PlaceCell<DESC, GX> (the same inlined code on the same operands: the same bits as PlaceCells) times a von Mises of
+// the theta phase, AFTER the scaling to [min_fr, max_fr]:
+//   dir = Agent.velocity / (1e-8 + |Agent.velocity|)            (the motion model's velocity: float64 state rows)
+//   s   = ((pos - centre) . dir) / sig_b                        (plain subtraction: no periodic wrap)
+//   D / 2 pi = 0.5 - s * precess_fraction / 2 - theta           (theta = theta_freq * (t mod 1 / theta_freq), revolutions)
+//   rate *= exp(kappa (cos D - 1)) * exp(kappa) / I0(kappa)
+// in fp32, the phase in revolutions (v_fract -> v_cos_f32), one exp2 for the von Mises.  GX: 0 or 3.
+struct ThetaPos {
+  PosQuad q;
+  v4f dx, dy;  // unit direction of motion (0 at rest: the preferred phase is then pi)
+};
+
+template <int DESC, int GX>
+struct ThetaPlaceCell {
+  typedef ThetaPos Pos;
+  static constexpr int LDS_DOUBLES = 1;
+  __device__ __forceinline__ void stage(double*) {}
+  PlaceCell<DESC, GX> base;
+  const float* tab;    // [n][4] = (centre x, centre y, k = -log2(e) / (2 w^2), precess_fraction / (2 sig_b))
+  const double* vx64;  // rows RIAB_S_VEL_X / _Y of the float64 state (T = 1)
+  const double* vy64;
+  float phase0;        // 0.5 - theta, revolutions
+  float k2;            // kappa * log2(e)
+  float norm;          // exp(kappa) / I0(kappa)
+  __device__ __forceinline__ Pos load(const RateArgs& a, int64_t off) const {
+    Pos P;
+    P.q = base.load(a, off);
+    const double* px = vx64 + off;
+    const double* py = vy64 + off;
+    const v4f vx = {(float)px[0], (float)px[1], (float)px[2], (float)px[3]};
+    const v4f vy = {(float)py[0], (float)py[1], (float)py[2], (float)py[3]};
+    const v4f sp{sqrtf(fmaf(vy.x, vy.x, vx.x * vx.x)), sqrtf(fmaf(vy.y, vy.y, vx.y * vx.y)),
+                 sqrtf(fmaf(vy.z, vy.z, vx.z * vx.z)), sqrtf(fmaf(vy.w, vy.w, vx.w * vx.w))};
+    const v4f inv = 1.0f / (sp + 1e-8f);
+    P.dx = vx * inv;
+    P.dy = vy * inv;
+    return P;
+  }
+  static constexpr int NP = 4;
+  static constexpr int CPB = 4;
+  __device__ __forceinline__ v4f eval(const float* p, const Pos& P) const { return base.eval(p, P.q); }
+  __device__ __forceinline__ float factor(float cx, float cy, float pf, float px, float py, float dx, float dy) const {
+    const float along = fmaf(py - cy, dy, (px - cx) * dx);
+    float rev = fmaf(-along, pf, phase0);
+    rev -= floorf(rev);  // v_fract: keep the hardware cosine in its accurate range
+    return __builtin_amdgcn_exp2f((__builtin_amdgcn_cosf(rev) - 1.0f) * k2) * norm;
+  }
+  __device__ __forceinline__ v4f modulation(const float* p, const Pos& P) const {
+    return v4f{factor(p[0], p[1], p[3], P.q.x.x, P.q.y.x, P.dx.x, P.dy.x), factor(p[0], p[1], p[3], P.q.x.y, P.q.y.y, P.dx.y, P.dy.y),
+               factor(p[0], p[1], p[3], P.q.x.z, P.q.y.z, P.dx.z, P.dy.z), factor(p[0], p[1], p[3], P.q.x.w, P.q.y.w, P.dx.w, P.dy.w)};
+  }
+};
+
+template <int DESC, int GX>
+__device__ __forceinline__ v4f post_scale(const ThetaPlaceCell<DESC, GX>& c, const float* p, const ThetaPos& P, v4f r) {
+  return r * c.modulation(p, P);
+}
+__device__ __forceinline__ v4f finish_rate(v4f r, const ThetaPos& P) { return finish_rate(r, P.q); }
 
 // ---- GridCells (reference Neurons.py:1172-1236) -------------------------------------------
 // phase of cosine i in revolutions: a_i - (x*bx_i + y*by_i); v_cos_f32 takes revolutions.

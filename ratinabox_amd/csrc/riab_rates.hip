@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void rate_kernel_wide(const RateArgs a, Cell c
       for (int i = 0; i < NP; ++i)
         p[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine), j * NP + i));
       v4f r = cell.eval(p, P);
-      r = finish_rate(r * a.fr_scale + a.fr_min, P);  // [0,1] -> [min_fr, max_fr]
+      r = finish_rate(post_scale(cell, p, P, r * a.fr_scale + a.fr_min), P);  // [0,1] -> [min_fr, max_fr]
       if (live) {
         // (NT: a launch of ONE row — a population's update() inside a closed loop, kernels that need the result behind it:
         // streamed and written through, nothing left for the dispatch's closing release to flush, riab_device.h; the
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void rate_kernel_generic(const RateArgs a, Cel
       for (int i = 0; i < NP; ++i)
         p[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine[i]), j));
       v4f r = cell.eval(p, P);
-      r = finish_rate(r * a.fr_scale + a.fr_min, P);
+      r = finish_rate(post_scale(cell, p, P, r * a.fr_scale + a.fr_min), P);
       if (live) {
         store_stream<RIAB_STORE_NT>(a.rates + off, r);
         if (SPK == 1) spike_store<false>(a, r, off, step, (uint32_t)(cb + j), group);
@@ -827,6 +827,80 @@ extern "C" int riab_place_cells(const RiabEnv* env, const RiabRateIO* io, const 
     case RIAB_GEOM_GEODESIC: return place_dispatch<2>(env, io, cells, n, description, top_hat_width, s);
     default: return RIAB_EINVAL;
   }
+}
+
+// exp(kappa) / I0(kappa), float64: the power series of I0 has positive terms only (no cancellation at any kappa it
+// does not overflow at); beyond that the leading terms of the asymptotic expansion
+static double von_mises_peak(double kappa) {
+  if (kappa > 600.0) {
+    const double y = 1.0 / (8.0 * kappa);
+    return sqrt(2.0 * 3.14159265358979323846 * kappa) / (1.0 + y * (1.0 + y * (4.5 + y * 37.5)));
+  }
+  const double q = 0.25 * kappa * kappa;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 4096; ++k) {
+    term *= q / ((double)k * (double)k);
+    sum += term;
+    if (term < 1e-18 * sum) break;
+  }
+  return exp(kappa) / sum;
+}
+
+struct ThetaMod {
+  const float* tab;
+  const double* vx64;
+  const double* vy64;
+  float phase0, k2, norm;
+};
+template <int DESC, int GX>
+static int launch_theta(const RiabRateIO* io, int n, const PlaceCell<DESC, GX>& base, const ThetaMod& m, hipStream_t s) {
+  return launch_rate(io, n, ThetaPlaceCell<DESC, GX>{base, m.tab, m.vx64, m.vy64, m.phase0, m.k2, m.norm}, s);
+}
+
+template <int GX>
+static int theta_place_dispatch(const RiabEnv* env, const RiabRateIO* io, const float* cells, int n, int desc, float thw,
+                                double kappa, double theta_rev, const double* vel_x, const double* vel_y, hipStream_t s) {
+  PlaceCell<RIAB_PC_GAUSSIAN, GX> c;
+  c.tab = cells;
+  c.scale = (float)env->scale;
+  c.half_scale = (float)(env->scale / 2);
+  c.top_hat_w2 = thw * thw;
+  c.walls = env->walls;
+  c.n_internal = 0;
+  c.e0 = env->extent[0]; c.e1 = env->extent[1]; c.e2 = env->extent[2]; c.e3 = env->extent[3];
+  c.shape = make_env_shape(env);
+  c.lds = nullptr;
+  const float phase0 = (float)(0.5 - theta_rev), k2 = (float)(kappa * 1.4426950408889634), norm = (float)von_mises_peak(kappa);
+  auto go = [&](auto base) { return launch_theta(io, n, base, ThetaMod{cells, vel_x, vel_y, phase0, k2, norm}, s); };
+  switch (desc) {
+    case RIAB_PC_GAUSSIAN: return go(c);
+    case RIAB_PC_GAUSSIAN_THRESHOLD: return go(c.template as<RIAB_PC_GAUSSIAN_THRESHOLD>());
+    case RIAB_PC_DIFF_OF_GAUSSIANS: return go(c.template as<RIAB_PC_DIFF_OF_GAUSSIANS>());
+    case RIAB_PC_TOP_HAT: return go(c.template as<RIAB_PC_TOP_HAT>());
+    default: return RIAB_EINVAL;  // one_hot has no width (contribs/PhasePrecessingPlaceCells.py:58-63)
+  }
+}
+
+extern "C" int riab_phase_precessing_place_cells(const RiabEnv* env, const RiabRateIO* io, const float* cells, int32_t n,
+                                                 int32_t description, int32_t geometry, float top_hat_width, double kappa,
+                                                 double theta_rev, const double* vel_x, const double* vel_y,
+                                                 riab_stream_t stream) {
+  if (!env || !cells || !vel_x || !vel_y || !(kappa >= 0.0) || !(theta_rev == theta_rev)) return RIAB_EINVAL;
+  const int rc = check_io(io, n, true, false);
+  if (rc) return rc;
+  if (io->T != 1) return RIAB_EINVAL;  // the state holds the current step only
+  if (((uintptr_t)vel_x | (uintptr_t)vel_y) & 31) return RIAB_EALIGN;
+  if (description != RIAB_PC_GAUSSIAN && description != RIAB_PC_GAUSSIAN_THRESHOLD &&
+      description != RIAB_PC_DIFF_OF_GAUSSIANS && description != RIAB_PC_TOP_HAT)
+    return RIAB_EINVAL;
+  if (geometry != RIAB_GEOM_EUCLIDEAN) {
+    if (geometry != RIAB_GEOM_LINE_OF_SIGHT && geometry != RIAB_GEOM_GEODESIC) return RIAB_EINVAL;
+    return RIAB_EUNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (env->periodic)
+    return theta_place_dispatch<3>(env, io, cells, n, description, top_hat_width, kappa, theta_rev, vel_x, vel_y, s);
+  return theta_place_dispatch<0>(env, io, cells, n, description, top_hat_width, kappa, theta_rev, vel_x, vel_y, s);
 }
 
 template <int GX>

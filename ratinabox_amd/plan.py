@@ -37,7 +37,9 @@ def _attach_fused(plan, agent):
                  "riab_plan_set_compute_units")
 
 
-_FUSABLE = ("PlaceCells", "GridCells", "HeadDirectionCells")   # (what csrc/riab_step1.hip step1_supported admits)
+# (what csrc/riab_step1.hip step1_supported admits, by exact class name: VelocityCells and contribs.PhasePrecessingPlaceCells
+# read the float64 state — their own kernels after the step kernel, in list order)
+_FUSABLE = ("PlaceCells", "GridCells", "HeadDirectionCells")
 
 
 def _settle_fused(plan):
@@ -186,6 +188,7 @@ class StepPlan:
                                           _L.ptr(agent._diag))
         if not self._h:
             raise _L.RiabError("riab_plan_create failed")
+        _L.check(_L.lib.riab_plan_set_clock(self._h, float(agent.t)), "riab_plan_set_clock")   # (Agent.t: the theta phase)
         self._forced = _ForcedRows(agent, self._h, block=self.capacity) if agent.use_imported_trajectory else None
         self._step_fn = _L.lib.riab_plan_step
         raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -452,6 +455,7 @@ class AutoStepper:
         if not self._h:
             raise _L.RiabError("riab_plan_create failed")
         self._h = _L.C.c_void_p(self._h)
+        _L.check(_L.lib.riab_plan_set_clock(self._h, float(agent.t)), "riab_plan_set_clock")
         self._forced = _ForcedRows(agent, self._h) if agent.use_imported_trajectory else None
         self._traj_id = getattr(agent, "_trajectory_id", 0)
         self._index, self._pops, self._keys = {}, [], []
