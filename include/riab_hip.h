@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RIAB_ABI_VERSION 10
+#define RIAB_ABI_VERSION 11
 #define RIAB_MAX_WALLS 64     /* walls staged in LDS by the motion / BVC / line-of-sight kernels */
 #define RIAB_MAX_TEST_ANGLES 360
 #define RIAB_STATE_ROWS 12    /* rows of the agent state matrix, see below */
@@ -1025,6 +1025,70 @@ int riab_td_update(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_l
  * td: at most 8). */
 int riab_td_reset(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers, float* const* rows,
                   int32_t n_rows, const uint8_t* mask, riab_stream_t stream);
+
+/* ---- contribs.SubAgent: theta sequences (reference contribs/SubAgent.py) -----------------------------------------
+ * A SubAgent is an Agent whose position is a function of another Agent's (the lead's) state.  The entry points below
+ * compute that position on the device, [2][B] float64, ready to be the `forced_pos` of riab_agent_step(T = 1) on the
+ * SubAgent's own state.  lead_state: the lead's state matrix, device float64 [RIAB_STATE_ROWS][B].
+ *
+ * ThetaSequenceAgent (SubAgent.py:182-350): once per theta cycle the position sweeps from d_half behind the lead, along
+ * the lead's own past, to d_half ahead of it, along a future simulated by the motion model.  The theta phase is the same
+ * for every lane and is computed by the host (`(t % T) / T` on the lead's clock, the reference's expression), which also
+ * picks the branch: */
+enum {
+  RIAB_THETA_NONE = 0,    /* before / after the sweep: NaN (SubAgent.py:270, 337) */
+  RIAB_THETA_BEHIND = 1,  /* look behind: interpolate the ring of past records (:274-300) */
+  RIAB_THETA_AHEAD = 2    /* look ahead: interpolate the lane's future table (:328-334) */
+};
+/* diag of the two entry points: device int32 [4] or NULL, atomically accumulated over the lanes b < n_agents (B is the
+ * padded row length; the padding lanes b >= n_agents are computed like the others and not counted; 0 <= n_agents <= B) */
+enum {
+  RIAB_THETA_DIAG_BEHIND = 0,   /* look-behind steps where the reference would have raised (fewer than two points in
+                                   true_distances[idx-3:idx+3], or the abscissa outside them): the lane gets NaN */
+  RIAB_THETA_DIAG_AHEAD = 1,    /* look-ahead steps whose abscissa lies outside the future table: NaN */
+  RIAB_THETA_DIAG_ROLLOUT = 2,  /* rollouts that used all K steps without covering forward_distance */
+  RIAB_THETA_DIAG_FAR = 3       /* positions dropped (NaN) because they were further than d_half from the lead */
+};
+
+/* One ThetaSequenceAgent.update() up to the forced step.  Every call first appends the lead's (distance travelled, x,
+ * y) as record number `n_records` (the count of records appended before this call; the caller adds one per call) to
+ * ring, device float64 [capacity][3][B], slot n_records % capacity — the reference's recent_data_stash, whose window is
+ * always the newest min(lookback, records) records (:283-286); capacity >= lookback >= 1.  Then, by `branch`:
+ *   RIAB_THETA_BEHIND  newest distance < d_half: the lead's position.  Otherwise x = newest - (m*phase + c), c = d_half /
+ *                      theta_frac, m = -2c; idx = the first index of the window that minimises |distance - x| (found by
+ *                      bisection: the distances do not decrease); scipy's linear interp1d over the records
+ *                      [idx-3 : idx+3] of the window (Python slice rules).
+ *   RIAB_THETA_AHEAD   x = the lead's distance + (m*phase + c), c = -d_half / theta_frac, m = -2c; scipy's linear
+ *                      interp1d over the count[b] + 1 entries of the lane's future table (future [K+1][3][B], count
+ *                      int32 [B]: what riab_theta_sequence_rollout wrote).
+ * Last (:341-343): a position further than d_half from the lead's — periodic wrap included (env->periodic, env->scale)
+ * — becomes NaN.  pos_out: device float64 [2][B].  RIAB_EINVAL: null pointers, capacity < lookback, lookback < 1,
+ * an unknown branch, d_half or theta_frac <= 0, RIAB_THETA_AHEAD without a table or with K < 1. */
+int riab_theta_sequence_step(const RiabEnv* env, const double* lead_state, int64_t B, int64_t n_agents, double* ring,
+                             int32_t capacity, int32_t lookback, int64_t n_records, int32_t branch, double phase, double d_half,
+                             double theta_frac, const double* future, const int32_t* count, int32_t K, double* pos_out,
+                             int32_t* diag, riab_stream_t stream);
+
+/* The forward rollout of a theta cycle (SubAgent.py:305-327), one lane per agent: rows POS, VEL, ROT_VEL and DIST of
+ * forward_state (the ForwardSequenceAgent's state matrix, [RIAB_STATE_ROWS][B]) are set to the lead's, then the lane is
+ * advanced by the motion model of riab_agent_step (`motion`: built for dt_forward; the same device code, so a rollout
+ * step has the bits of a riab_agent_step(T = 1) step on the same operands and the same wave) while its distance
+ * travelled < the lead's + forward_distance — at most K steps, where the reference loops without bound
+ * (RIAB_THETA_DIAG_ROLLOUT counts lanes that ran out).  future [K+1][3][B]: entry 0 the start, entry k the (distance, x,
+ * y) after step k, written up to count[b], the number of steps the lane took.  forward_state is left as the lane's last
+ * counted step left it.  Noise: z_in device float64 [K][2][B] or NULL => Philox keyed by (seed; step0 + k, agent id),
+ * exactly as riab_agent_step draws; z_out [K][2][B] or NULL records the normals (rows past a wave's last step are not
+ * written).  The caller advances its step counter by K per rollout whatever the lanes used.  motion_diag: the
+ * ForwardSequenceAgent's riab_agent_step counters (they include the steps a lane takes while it waits for its wave).
+ * RIAB_EINVAL: null pointers, K < 1, forward_distance <= 0, a motion with drift. */
+int riab_theta_sequence_rollout(const RiabEnv* env, const RiabMotion* motion, const double* lead_state,
+                                double* forward_state, int64_t B, int64_t n_agents, int64_t agent_id0, const double* z_in,
+                                double* z_out,
+                                uint64_t seed, uint64_t step0, int32_t K, double forward_distance, double* future,
+                                int32_t* count, int32_t* motion_diag, int32_t* diag, riab_stream_t stream);
+
+/* ShiftAgent (SubAgent.py:466-478): pos_out [2][B] = lead position + lead head direction * shift_m. */
+int riab_shift_agent_position(const double* lead_state, int64_t B, double shift_m, double* pos_out, riab_stream_t stream);
 
 /* sizeof of the ABI's structs as compiled into the library (which: 0 RiabEnv, 1 RiabMotion, 2 RiabRateIO,
  * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at

@@ -13,7 +13,7 @@ import torch  # noqa: F401
 
 from . import _build
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_WALLS = 64
 STATE_ROWS = 12
 HIST_ROWS = 8
@@ -122,6 +122,8 @@ TW_TERMINAL, TW_GOAL_LIST, TW_ROWS = 7, 8, 24
 
 POP_KINDS = {"place": 0, "grid": 1, "hdc": 2, "bvc": 3, "ovc": 4, "ff": 5, "velocity": 6, "speed": 7, "random_spatial": 8,
              "theta_place": 9}
+THETA_NONE, THETA_BEHIND, THETA_AHEAD = 0, 1, 2                          # riab_hip.h RIAB_THETA_*
+THETA_DIAG_BEHIND, THETA_DIAG_AHEAD, THETA_DIAG_ROLLOUT, THETA_DIAG_FAR = range(4)
 EINVAL = -1
 EALIGN = -2
 ETOOBIG = -3
@@ -209,6 +211,13 @@ PROTOTYPES = {
                                  C.c_void_p, C.c_int64, C.c_void_p]),
     "riab_td_reset": (C.c_int, [C.POINTER(RiabTDParams), C.POINTER(RiabTDLayer), C.c_int32, C.POINTER(C.c_void_p),
                                 C.c_int32, C.c_void_p, C.c_void_p]),
+    "riab_theta_sequence_step": (C.c_int, [C.POINTER(RiabEnv), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "riab_theta_sequence_rollout": (C.c_int, [C.POINTER(RiabEnv), C.POINTER(RiabMotion), C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32,
+                                              C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "riab_shift_agent_position": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
     "riab_fill": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "riab_plan_create": (C.c_void_p, [C.POINTER(RiabEnv), C.POINTER(RiabMotion), C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),

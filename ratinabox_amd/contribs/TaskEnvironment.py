@@ -296,6 +296,9 @@ class TaskEnvironment(Environment):
         if self._agent is not None:
             raise NotImplementedError("one batched Agent per TaskEnvironment: use Agent(params={'n_agents': B})")
         agent = agents
+        if getattr(agent, "_is_subagent", False):
+            raise NotImplementedError("a SubAgent (contribs.SubAgent) cannot be the agent of a TaskEnvironment: its position "
+                                      "is a function of its lead's, not of an action")
         if agent.dt != self.dt:
             raise NotImplementedError("Does not yet support agents with different dt from envrionment")
         assert self.boundary_conditions == "solid", \

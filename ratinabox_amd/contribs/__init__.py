@@ -5,5 +5,6 @@ the reference's way —
     from ratinabox_amd.contribs.ValueNeuron import ValueNeuron
     from ratinabox_amd.contribs.SuccessorFeatures import SuccessorFeatures
     from ratinabox_amd.contribs.PhasePrecessingPlaceCells import PhasePrecessingPlaceCells
+    from ratinabox_amd.contribs.SubAgent import SubAgent, ThetaSequenceAgent, ShiftAgent, UnrelatedAgent
 """
-__all__ = ["TaskEnvironment", "ValueNeuron", "SuccessorFeatures", "PhasePrecessingPlaceCells"]
+__all__ = ["TaskEnvironment", "ValueNeuron", "SuccessorFeatures", "PhasePrecessingPlaceCells", "SubAgent"]
