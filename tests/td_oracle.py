@@ -4,8 +4,57 @@ contribs/ValueNeuron.py:59-113), batched: test infrastructure only (the frozen o
 In float64 and with one lane it reproduces the reference bit for bit (tests/test_td_cpu.py pins it on the fixtures
 tests/golden/td_*.npz); with B lanes the weight change is the mean over the lanes of the per-lane outer products, the
 batched semantics of the product.  Run in `dtype=np.float32` it measures what plain fp32 arithmetic costs on a given
-run: the GPU tests derive their allowance from that figure."""
+run: the GPU tests derive their allowance from that figure (`check`).  `one_step` is the same rule for ONE step on arrays
+handed in as the kernels get them (V and act' given): tests/test_gpu_td_shapes.py drives the operators against it."""
 import numpy as np
+
+FACTOR = 4.0     # kernel allowance over the fp32 NumPy run
+
+
+def check(label, got, ref, err32, scale, keys):
+    """|got - ref| <= FACTOR * (fp32 NumPy error) * scale per quantity; prints the measured ratio first."""
+    lines, bad = [], []
+    for k in keys:
+        e = float(np.abs(np.asarray(got[k], float) - ref[k]).max()) / scale[k]
+        lines.append(f"{k}: kernel {e:.2e}, fp32 NumPy {err32[k]:.2e}, ratio {e / max(err32[k], 1e-300):.2f}")
+        if not e <= FACTOR * err32[k]:
+            bad.append(k)
+    print(f"[{label}] " + "; ".join(lines))
+    assert not bad, (label, bad, lines)
+
+
+def trace_step(f, dt, tau_e, phi, e):
+    """e <- dt * phi + (1 - dt / tau_e) * e in the arithmetic `f` (tau_e == 0: e <- phi)."""
+    if tau_e == 0:
+        return phi.copy()
+    return dt * phi + (f(1) - dt / tau_e) * e
+
+
+def weight_step(f, dt, eta, L2, B, w, g, e):
+    """W <- W + dt * eta * (g e^T) / B - eta * dt * L2 * W in the arithmetic `f`; g (n, B), e (n_in, B), w (n, n_in)."""
+    G = np.matmul(g, e.T) / f(B)
+    dw = dt * eta * G - eta * dt * L2 * w
+    return (w + dw).astype(f)
+
+
+def one_step(ws, traces, phis, v, v_last, prime, reward, dt, tau, tau_e, eta, L2, dtype=np.float64):
+    """ONE step of the rule on given arrays, the way the kernels are handed them (V and act' are inputs, not computed):
+    td_forward_tail (dV/dt, the traces) followed by td_update (TD error, weights).  Every array holds the B real lanes
+    only: ws[l] (n, n_in_l), traces[l] / phis[l] (n_in_l, B), v / v_last / prime (n, B), reward a scalar, (n,), (B,) or
+    (n, B).  Returns dict(dvdt, td, traces, ws) in `dtype`; the inputs are left as they are."""
+    f = dtype
+    dt, tau, tau_e, eta, L2 = f(dt), f(tau), f(tau_e), f(eta), f(L2)
+    v, v_last, prime = (np.asarray(a, dtype=f) for a in (v, v_last, prime))
+    n, B = v.shape
+    r = np.asarray(reward, dtype=f)
+    if r.ndim == 1 and r.shape[0] == n:
+        r = r[:, None]
+    dvdt = (v - v_last) / dt
+    new_traces = [trace_step(f, dt, tau_e, np.asarray(p, dtype=f), np.asarray(e, dtype=f)) for p, e in zip(phis, traces)]
+    td = (r + dvdt - v / tau) * np.ones((n, B), dtype=f)
+    g = td * prime
+    new_ws = [weight_step(f, dt, eta, L2, B, np.asarray(w, dtype=f), g, e) for w, e in zip(ws, new_traces)]
+    return {"dvdt": dvdt, "td": td, "traces": new_traces, "ws": new_ws}
 
 
 class TDOracle:
@@ -44,10 +93,7 @@ class TDOracle:
         self.dVdt = (V - self.V) / self.dt
         self.V = V.astype(f)
         for l, p in enumerate(phis):
-            if self.tau_e == 0:
-                self.traces[l] = p.copy()
-            else:
-                self.traces[l] = self.dt * p + (f(1) - self.dt / self.tau_e) * self.traces[l]
+            self.traces[l] = trace_step(f, self.dt, self.tau_e, p, self.traces[l])
 
     def update_weights(self, reward):
         """reward: scalar, (n,) (one per neuron), (B,) (one per lane; for n == B read as one per neuron) or (n, B)."""
@@ -57,9 +103,7 @@ class TDOracle:
         self.td = (r + self.dVdt - self.V / self.tau) * np.ones((self.n, self.B), dtype=self.f)
         g = self.td * self.prime
         for l, w in enumerate(self.ws):
-            G = np.matmul(g, self.traces[l].T) / self.f(self.B)
-            dw = self.dt * self.eta * G - self.eta * self.dt * self.L2 * w
-            self.ws[l] = (w + dw).astype(self.f)
+            self.ws[l] = weight_step(self.f, self.dt, self.eta, self.L2, self.B, w, g, self.traces[l])
 
     def reset(self, mask=None):
         m = np.ones(self.B, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)

@@ -214,3 +214,90 @@ def test_refusals(cpu_agent):
     shard = riab.Agent(riab.Environment({}), {"n_agents": 4, "device": "cpu", "agent_id0": 8})
     with pytest.raises(NotImplementedError, match="shard"):
         ValueNeuron(shard, {"input_layers": [riab.PlaceCells(shard, {"n": 4})]})
+
+
+# ---- the shapes of tests/test_gpu_td_shapes.py ---------------------------------------------------------------------
+def test_one_step_oracle_is_the_oracle_step():
+    """tdo.one_step (V and act' given) against TDOracle (V computed): the same bits, in float64 and in float32."""
+    rng = np.random.RandomState(6)
+    n, n_ins, B = 5, (7, 3), 6
+    kw = dict(dt=0.05, tau=1.5, tau_e=0.4, eta=0.02, L2=0.003)
+    for f in (np.float64, np.float32):
+        o = tdo.TDOracle([rng.normal(size=(n, k)) * 0.3 for k in n_ins], activation="relu", B=B, dtype=f, **kw)
+        for step in range(3):
+            phis, r = [rng.uniform(size=(k, B)) for k in n_ins], rng.normal(size=(n, B))
+            ws, traces, v_last = [w.copy() for w in o.ws], [e.copy() for e in o.traces], o.V.copy()
+            o.update(phis)
+            o.update_weights(r)
+            got = tdo.one_step(ws, traces, phis, o.V, v_last, o.prime, r, dtype=f, **kw)
+            np.testing.assert_array_equal(got["dvdt"], o.dVdt)
+            np.testing.assert_array_equal(got["td"], o.td)
+            for l in range(2):
+                np.testing.assert_array_equal(got["traces"][l], o.traces[l])
+                np.testing.assert_array_equal(got["ws"][l], o.ws[l])
+                assert got["ws"][l].dtype == f and not np.array_equal(got["ws"][l], ws[l])
+
+
+def test_integer_cases_are_exact_in_fp32():
+    """Every case keeps |partial sum of G| <= 36 B below 2^24, where fp32 holds every integer: the order of the kernel's
+    additions cannot matter.  The generator stays inside the ranges the bound rests on, and the float64 BLAS product the
+    reference takes equals NumPy's int64 product."""
+    from tests import td_shapes as sh
+    all_cases = sh.cases()
+    assert len(all_cases) == len({c.name for c in all_cases}) >= 45
+    for c in all_cases:
+        assert sh.exactness_bound(c.B) == c.B * 36 < 2 ** 24, c
+        assert 1 <= c.B <= c.Bp and c.Bp % 4 == 0 and len(c.layers) <= sh.MAX_LAYERS, c
+    assert sh.INT_CONSTS == [0.5, 1.0, 1.0, 1.0, 0.0]
+    for c in [c for c in all_cases if c.Bp <= 36 and c.n <= 129]:
+        a = sh.integer_inputs(c)
+        for x in a["phi"] + a["trace"]:
+            assert x.dtype == np.float32 and set(np.unique(x)) <= {0.0, 2.0, 4.0}
+        for k in ("v", "dvdt", "reward"):
+            assert np.array_equal(a[k], np.round(a[k])) and np.abs(a[k]).max() <= 3
+        assert set(np.unique(a["prime"])) <= {0.0, 1.0}
+        assert np.array_equal((a["v"] - a["v_last"]) / np.float32(0.5), a["dvdt"])
+        ref = sh.integer_reference(c, a)
+        g = ref["td"] * a["prime"][:, :c.B].astype(np.int64)
+        for G, e, wt in zip(ref["G"], ref["traces"], ref["wt"]):
+            assert np.array_equal(G, np.matmul(g, e.T)) and G.dtype == np.int64
+            assert np.array_equal(wt.astype(np.float64).T * c.B, G * 0.5) or c.B & (c.B - 1)   # B a power of two: exact
+            assert wt.shape == (e.shape[0], c.n)
+    # two cases never share a pattern, nor two layers of one case
+    a = sh.integer_inputs(sh.Case("x", 3, [40, 40], 30, 32, "f32_nb"))
+    assert not np.array_equal(a["phi"][0], a["phi"][1]) and not np.array_equal(a["trace"][0], a["trace"][1])
+
+
+def test_case_list_reaches_the_paths_it_claims():
+    """MT and the row groups by the launcher's rule, the chunk count from riab_td_workspace / (n sum n_in) (no GPU
+    needed): every td_grad_kernel<MT, FUSE> row-tile count, two and three row groups, eight layers, a ragged wave and a
+    ragged 128-row block, Bp % 32 != 0, a short last chunk and eight slabs per chunk are all in the list."""
+    from ratinabox_amd import ops
+    from tests import td_shapes as sh
+    seen = set()
+    for c in sh.cases():
+        path = sh.launch_path(c.n, c.layers, c.Bp)
+        assert (path["mt"], path["groups"]) == sh.ROWS[c.n], c
+        floats = ops.td_workspace_floats(c.n, c.layers, c.Bp)
+        assert floats % (c.n * sum(c.layers)) == 0 and floats // (c.n * sum(c.layers)) == path["n_chunks"], c
+        assert (path["n_chunks"] - 1) * path["slabs"] < path["n_slabs"] <= path["n_chunks"] * path["slabs"]
+        if c.layers == sh.LAYER_SETS[sh.MODEST_LAYERS]:
+            assert (path["slabs"], path["n_chunks"], path["last"]) == sh.BATCHES[(c.B, c.Bp)], c
+        seen.add(("mt", path["mt"]))
+        seen.add(("groups", path["groups"]))
+        seen.add(("layers", len(c.layers)))
+        seen.add(("reward", c.reward, c.n))
+        for what, hit in (("short last chunk", path["last"] < path["slabs"]), ("Bp % 32", c.Bp % 32 != 0),
+                          ("eight slabs", path["slabs"] == 8), ("padded lanes", c.B < c.Bp),
+                          ("ragged wave", any(k % 32 for k in c.layers)),
+                          ("ragged block", any(k > 128 and k % 128 for k in c.layers))):
+            if hit:
+                seen.add((what, c.n in sh.WIDE and c.n))
+    want = {("mt", m) for m in (1, 2, 4, 8)} | {("groups", g) for g in (1, 2, 3)} | {("layers", k) for k in (1, 2, 3, 8)}
+    want |= {("reward", r, n) for r in sh.REWARD_FORMS for n in sh.WIDE}
+    want |= {(w, n) for w in ("short last chunk", "Bp % 32", "eight slabs", "padded lanes", "ragged wave", "ragged block")
+             for n in sh.WIDE}
+    assert want <= seen, want - seen
+    assert sh.launch_path(257, [127, 129], 4152) == dict(mt=8, groups=2, blocks=3, n_slabs=130, slabs=3, n_chunks=44, last=1)
+    with pytest.raises(Exception):
+        ops.td_workspace_floats(129, [4] * (sh.MAX_LAYERS + 1), 36)
