@@ -41,7 +41,8 @@ enum {
   RIAB_OK = 0,
   RIAB_EINVAL = -1,       /* null pointer / negative size / bad enum */
   RIAB_EALIGN = -2,       /* B % 4 != 0 or misaligned row pointer */
-  RIAB_ETOOBIG = -3,      /* more walls / test angles than the LDS staging allows */
+  RIAB_ETOOBIG = -3,      /* more walls / test angles / objects than the LDS staging allows (objects: the LDS one
+                           * workgroup can be given / 768 bytes = 213 on gfx950) */
   RIAB_EUNSUPPORTED = -4, /* combination not implemented on device */
   RIAB_EFULL = -5,        /* a step plan's history chunk has no free row left */
   RIAB_EPARTIAL = -6,     /* riab_simulate_*: a launch failed AFTER the trajectory kernel had been launched: the agent
@@ -348,7 +349,13 @@ int riab_boundary_vector_cells_windowed(const RiabEnv* env, const RiabRateIO* io
  *  cells         device float32 [n][6] = (a*mu_d, a, cos(mu_theta), sin(mu_theta), kappa*log2(e),
  *                tuning type), a = sqrt(log2(e)/2)/sigma_d
  *  walls_occlude line_of_sight geometry: an object behind an internal wall (env->walls[4:]) is
- *                at distance 1000 (Neurons.py:1938-1941); egocentric needs io->hd_x / hd_y */
+ *                at distance 1000 (Neurons.py:1938-1941); egocentric needs io->hd_x / hd_y
+ * The kernel stages 768 bytes of LDS per object: n_objects is bounded by the dynamic LDS one workgroup can be
+ * given on the device (the larger of hipDeviceAttributeMaxSharedMemoryPerBlock and ...PerMultiprocessor / 768: 213
+ * objects in gfx950's 160 KiB; above
+ * 85 the kernel's limit is raised first).  More objects — or a runtime that will not raise the limit — return
+ * RIAB_ETOOBIG with nothing launched; riab_simulate and riab_plan_add refuse such a population the same way, before
+ * anything is in flight.  walls_occlude in a periodic room: RIAB_EUNSUPPORTED (Environment.py:711-713). */
 int riab_object_vector_cells(const RiabEnv* env, const RiabRateIO* io, const float* objects,
                              const int32_t* object_types, int32_t n_objects, const float* cells, int32_t n,
                              int32_t walls_occlude, int32_t egocentric, riab_stream_t stream);

@@ -187,6 +187,11 @@ class Environment:
         self.objects["objects"] = np.append(self.objects["objects"], object, axis=0)
         self.objects["object_types"] = np.append(self.objects["object_types"], np.array([type], int), axis=0)
         self.n_object_types = len(np.unique(self.objects["object_types"]))
+        # a recorded step plan holds the device tables of the object list as it was: close it, so that its next step()
+        # refuses instead of computing with the old objects (update() and simulate() key their tables on content)
+        for ag in self.Agents:
+            if getattr(ag, "_plan", None) is not None:
+                ag._plan.close()
 
     # -- sampling (Environment.py:560-633) ------------------------------------------------
     def sample_positions(self, n=10, method="uniform_jitter"):

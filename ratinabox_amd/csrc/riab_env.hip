@@ -57,9 +57,10 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const EnvQuery q, const d
   for (int64_t i = blockIdx.y; i < N1; i += gridDim.y) {
     const double ax = x1[i], ay = y1[i];
     double dx = ax - bx, dy = ay - by;
-    if (q.periodic) {  // Environment.py:670-674
-      if (fabs(dx) > hs) dx = -copysign(q.scale - fabs(dx), dx);
-      if (fabs(dy) > hs) dy = -copysign(q.scale - fabs(dy), dy);
+    if (q.periodic) {  // Environment.py:670-674: -sign(v) (scale - |v|); scale - |v| is negative where a room wider than
+      // `scale` (aspect > 1) separates two points by more than `scale`, and keeps its sign
+      if (fabs(dx) > hs) dx = dx > 0.0 ? fabs(dx) - q.scale : q.scale - fabs(dx);
+      if (fabs(dy) > hs) dy = dy > 0.0 ? fabs(dy) - q.scale : q.scale - fabs(dy);
     }
     const int64_t o = i * N2 + j;
     if (vec_x) vec_x[o] = dx;

@@ -11,7 +11,11 @@
 // (d, cos, sin of the bearing) per (object, position) in LDS — the occlusion predicate in float64
 // sign logic — stage B: wave w owns cells c = w (mod 4) and, per cell, walks the objects of its
 // type with one fused exponent per term.  No trigonometry in the kernel: cos(beta - hb - phi) is
-// assembled from the unit vectors.
+// assembled from the unit vectors, and near a cell's peak 1 - cos from their difference (`one_minus_cos`).
+//
+// Stage A keeps 3 * 64 floats = 768 bytes of LDS per object: up to 85 objects fit the 64 KiB every launch may ask
+// for, more need the kernel's dynamic-LDS limit raised, and what one workgroup can be given at all (160 KiB on
+// gfx950: 213 objects) bounds the object count (`ovc_object_limit`; more are refused with RIAB_ETOOBIG).
 #include "riab_device.h"
 
 namespace riab {
@@ -41,6 +45,18 @@ struct OvcArgs {
   int64_t other_ld;
 };
 
+// 1 - cos(delta) between the unit vectors (c, s) and (cphi, sphi).  The product form 1 - (c cphi + s sphi) carries the
+// rounding of the cosine, ~1e-7 ABSOLUTE, which kappa = 1 / sigma_angle^2 (3283 at 1 degree) multiplies in the exponent:
+// near the peak, where the rate is large, that is 1e-4 of it.  The chord |u - v|^2 / 2 is the same quantity with a
+// RELATIVE error of ~1e-7 (the differences are exact-ish by Sterbenz; unit-norm errors enter squared) and is used where
+// the cosine exceeds 0.75; further out the two forms are equally good in relative terms and the product form, whose
+// exponent the tails of every wider tuning were validated with, is kept bit for bit.
+__device__ __forceinline__ float one_minus_cos(float c, float s, float cphi, float sphi) {
+  const float cosd = fmaf(c, cphi, s * sphi);
+  const float dc = c - cphi, ds = s - sphi;
+  return cosd > 0.75f ? 0.5f * fmaf(ds, ds, dc * dc) : 1.0f - cosd;
+}
+
 __global__ __launch_bounds__(256) void ovc_kernel(const OvcArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   float* s_d = reinterpret_cast<float*>(smem);  // [M][64]
@@ -68,9 +84,10 @@ __global__ __launch_bounds__(256) void ovc_kernel(const OvcArgs a) {
     const float ox = a.other_x ? a.other_x[t * a.other_ld + b] : objs[2 * m];
     const float oy = a.other_x ? a.other_y[t * a.other_ld + b] : objs[2 * m + 1];
     float vx = ox - px, vy = oy - py;  // object - position (Neurons.py:2038-2040)
-    if (a.periodic) {                  // Environment.py:670-674
-      if (fabsf(vx) > a.half_scale) vx = -copysignf(a.scale - fabsf(vx), vx);
-      if (fabsf(vy) > a.half_scale) vy = -copysignf(a.scale - fabsf(vy), vy);
+    if (a.periodic) {  // Environment.py:670-674: -sign(v) (scale - |v|), `scale` on both axes.  In a room wider than
+      // `scale` (aspect > 1) scale - |v| may be negative and keeps its sign (copysign would drop it)
+      if (fabsf(vx) > a.half_scale) vx = vx > 0.0f ? fabsf(vx) - a.scale : a.scale - fabsf(vx);
+      if (fabsf(vy) > a.half_scale) vy = vy > 0.0f ? fabsf(vy) - a.scale : a.scale - fabsf(vy);
     }
     float d = sqrtf(fmaf(vy, vy, vx * vx));
     if (a.occlude) {
@@ -102,8 +119,8 @@ __global__ __launch_bounds__(256) void ovc_kernel(const OvcArgs a) {
     for (int m = 0; m < a.M; ++m) {
       if (!a.other_x && types[m] != ctype) continue;  // wave-uniform
       const float tt = fmaf(s_d[m * 64 + lane], aa, -amu);
-      const float cosd = fmaf(s_c[m * 64 + lane], cphi, s_s[m * 64 + lane] * sphi);  // cos(bearing - phi)
-      acc += __builtin_amdgcn_exp2f(fmaf(-tt, tt, kap * (cosd - 1.0f)));
+      const float omc = one_minus_cos(s_c[m * 64 + lane], s_s[m * 64 + lane], cphi, sphi);  // 1 - cos(bearing - phi)
+      acc += __builtin_amdgcn_exp2f(fmaf(-tt, tt, -(kap * omc)));
     }
     if (live) {
       const float r = acc * a.fr_scale + a.fr_min;
@@ -129,6 +146,35 @@ __global__ __launch_bounds__(256) void ovc_kernel(const OvcArgs a) {
 
 using namespace riab;
 
+static constexpr size_t OVC_LDS_PER_OBJECT = sizeof(float) * 3 * 64;
+
+// The most objects stage A can hold on the current device: the LDS one workgroup can be given / 768 bytes (213 on
+// gfx950); -1 when no device answers.  Asked once per device.
+namespace riab {
+int ovc_object_limit() {
+  static int cached[64];  // 0 = not asked yet
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  if (dev >= 0 && dev < 64 && cached[dev]) return cached[dev];
+  // One workgroup may be given all of a compute unit's LDS; runtimes differ in which of the two attributes says so (the
+  // per-block figure can be the 64 KiB a launch gets without asking), so the larger one bounds the count and the checked
+  // hipFuncSetAttribute in launch_ovc has the last word.
+  int bytes = 0, per_cu = 0;
+  if (hipDeviceGetAttribute(&bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || bytes <= 0) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  if (hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess) (void)hipGetLastError();
+  if (per_cu > bytes) bytes = per_cu;
+  const int limit = (int)((size_t)bytes / OVC_LDS_PER_OBJECT);
+  if (dev >= 0 && dev < 64) cached[dev] = limit;
+  return limit;
+}
+}  // namespace riab
+
 static int launch_ovc(const RiabEnv* env, const RiabRateIO* io, const float* objects, const int32_t* object_types,
                       int32_t n_objects, const float* other_x, const float* other_y, int64_t other_ld,
                       const float* cells, int32_t n, int32_t walls_occlude, int32_t egocentric, hipStream_t stream) {
@@ -137,7 +183,15 @@ static int launch_ovc(const RiabEnv* env, const RiabRateIO* io, const float* obj
   if (io->u_in && !io->spikes) return RIAB_EINVAL;
   if (walls_occlude && env->periodic) return RIAB_EUNSUPPORTED;  // Environment.py:711-713
   if (walls_occlude && env->n_walls > 4 && !env->walls) return RIAB_EINVAL;
-  if (n_objects > 256) return RIAB_ETOOBIG;
+  const int limit = ovc_object_limit();
+  if (limit < 0) return RIAB_EINVAL;  // no device to launch on
+  if (n_objects > limit) return RIAB_ETOOBIG;
+  const size_t lds = OVC_LDS_PER_OBJECT * (size_t)n_objects;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)ovc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();  // the runtime will not give one workgroup that much: nothing is launched
+    return RIAB_ETOOBIG;
+  }
   OvcArgs a;
   a.pos_x = io->pos_x; a.pos_y = io->pos_y; a.hd_x = io->hd_x; a.hd_y = io->hd_y;
   a.pos_ld = io->pos_ld; a.P = io->T * io->B; a.B = io->B;
@@ -152,8 +206,6 @@ static int launch_ovc(const RiabEnv* env, const RiabRateIO* io, const float* obj
   a.scale = (float)env->scale; a.half_scale = (float)(env->scale / 2);
   a.walls = env->walls; a.objects = objects; a.types = object_types; a.cells = cells;
   a.other_x = other_x; a.other_y = other_y; a.other_ld = other_ld;
-  const size_t lds = sizeof(float) * 3 * 64 * (size_t)n_objects;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)ovc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(ovc_kernel, dim3((unsigned)((a.P + 63) / 64)), dim3(256), lds, stream, a);
   return (int)hipGetLastError();
 }

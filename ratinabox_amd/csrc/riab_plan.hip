@@ -353,8 +353,16 @@ extern "C" int riab_plan_set_agent_history(RiabPlan* p, float* hist_base, int64_
   return RIAB_OK;
 }
 
+namespace riab {
+int ovc_object_limit();  // riab_ovc.hip: the most objects the vector-cell kernel's LDS staging holds (-1: no device)
+}
+
 extern "C" int riab_plan_add(RiabPlan* p, const RiabPopulation* pop) {
   if (!p || !pop || pop->n <= 0 || pop->kind < RIAB_POP_PLACE || pop->kind > RIAB_POP_THETA_PLACE) return RIAB_EINVAL;
+  if (pop->kind == RIAB_POP_OVC) {  // (a plan that could not take its first step is refused when it is recorded)
+    const int limit = riab::ovc_object_limit();
+    if (limit >= 0 && pop->n_objects > limit) return RIAB_ETOOBIG;
+  }
   if (pop->kind == RIAB_POP_THETA_PLACE && (!pop->table || !(pop->theta_freq > 0.0) || !(pop->kappa >= 0.0))) return RIAB_EINVAL;
   if (pop->kind == RIAB_POP_FF) {
     if (pop->n_inputs <= 0 || pop->n_inputs > RIAB_FF_MAX_INPUTS || !pop->bias) return RIAB_EINVAL;

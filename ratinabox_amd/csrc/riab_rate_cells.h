@@ -337,19 +337,35 @@ struct HDCell {
     // (cos a, sin a) of a = atan2(y, x + 1e-6) is the vector (x + 1e-6, y) normalised.  (An fp32 atan2 +
     // cos pair costs 2e-5 of relative accuracy in the tails of narrow tunings; this form stays at the
     // rounding of the cosine itself.)
-    const v4f bx = hx + 1e-6f;
-    const v4f inv = {1.0f / sqrtf(fmaf(hy.x, hy.x, bx.x * bx.x)), 1.0f / sqrtf(fmaf(hy.y, hy.y, bx.y * bx.y)),
-                     1.0f / sqrtf(fmaf(hy.z, hy.z, bx.z * bx.z)), 1.0f / sqrtf(fmaf(hy.w, hy.w, bx.w * bx.w))};
-    P.cs = bx * inv;
-    P.sn = hy * inv;
+    {
+#pragma clang fp contract(off)  // (P.cs / P.sn are rounded products in every kernel: see eval)
+      const v4f bx = hx + 1e-6f;
+      const v4f inv = {1.0f / sqrtf(fmaf(hy.x, hy.x, bx.x * bx.x)), 1.0f / sqrtf(fmaf(hy.y, hy.y, bx.y * bx.y)),
+                       1.0f / sqrtf(fmaf(hy.z, hy.z, bx.z * bx.z)), 1.0f / sqrtf(fmaf(hy.w, hy.w, bx.w * bx.w))};
+      P.cs = bx * inv;
+      P.sn = hy * inv;
+    }
     return P;
   }
   static constexpr int NP = 3;
   static constexpr int CPB = 16;
+  // kappa (cos(angle - preferred) - 1): near the peak (cosine above 0.75) 1 - cos is taken from the chord between the
+  // two unit vectors, |u - v|^2 / 2, whose error is relative; the product form's is ~1e-7 absolute and kappa = 1 / spread^2
+  // (365 at 3 degrees, 3283 at 1) multiplies it in the exponent.  Further out the two are equally good relative to the
+  // exponent and the product form stays.  The rate kernels that share this must round alike (the open-loop run, the
+  // chunk pipeline, step plans and update() are compared bit for bit): every FMA here is written out and contraction is
+  // off, or the compiler fuses the multiply that made P.cs / P.sn (`bx * inv` in from_dirs) into `P.cs - cp` in the
+  // kernels where it sees both in one block and not in the others.
   __device__ __forceinline__ v4f eval(const float* p, const Pos& P) const {
+#pragma clang fp contract(off)
     if (MODE == 2) return P.speed;
     const float cp = p[0], sp = p[1], k2 = p[2];
-    const v4f e = (P.cs * cp + P.sn * sp - 1.0f) * k2;
+    const v4f cosd = __builtin_elementwise_fma(P.cs, v4f{cp, cp, cp, cp}, P.sn * sp);
+    const v4f dc = P.cs - cp, ds = P.sn - sp;
+    const v4f chord = __builtin_elementwise_fma(ds, ds, dc * dc) * -0.5f;
+    const v4f prod = cosd - 1.0f;
+    const v4f e = v4f{cosd.x > 0.75f ? chord.x : prod.x, cosd.y > 0.75f ? chord.y : prod.y, cosd.z > 0.75f ? chord.z : prod.z,
+                      cosd.w > 0.75f ? chord.w : prod.w} * k2;
     return v4f{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y), __builtin_amdgcn_exp2f(e.z),
                __builtin_amdgcn_exp2f(e.w)};
   }

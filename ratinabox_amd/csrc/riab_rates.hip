@@ -1049,7 +1049,7 @@ extern "C" const char* riab_strerror(int code) {
     case RIAB_OK: return "ok";
     case RIAB_EINVAL: return "invalid argument (null pointer, non-positive size or unknown enum)";
     case RIAB_EALIGN: return "agent axis not a multiple of 4 or row pointer not 16-byte aligned";
-    case RIAB_ETOOBIG: return "too many walls / test angles for the LDS staging";
+    case RIAB_ETOOBIG: return "too many walls / test angles / objects for the LDS staging (vector cells: 768 bytes per object, 213 objects in 160 KiB)";
     case RIAB_EUNSUPPORTED: return "combination not supported on device";
     case RIAB_EFULL: return "a step plan's history chunk is full: attach a new chunk";
     case RIAB_EPARTIAL: return "a launch failed after the trajectory kernel had been launched: the state has advanced, the rates of this call are incomplete";

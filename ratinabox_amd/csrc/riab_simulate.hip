@@ -503,13 +503,22 @@ static int launch_pop_rows(const RiabEnv* env, const RiabPopulation* pops, int i
   return rc;
 }
 
+namespace riab {
+int ovc_object_limit();  // riab_ovc.hip: the most objects the vector-cell kernel's LDS staging holds (-1: no device)
+}
+
 static int check_populations(const RiabPopulation* pops, int32_t n_pops, int32_t T) {
   for (int i = 0; i < n_pops; ++i) {
     const RiabPopulation& q = pops[i];
     if (q.n <= 0 || !q.rates_base || q.capacity_rows < T) return RIAB_EINVAL;
     switch (q.kind) {
       case RIAB_POP_PLACE: case RIAB_POP_GRID: case RIAB_POP_HDC: case RIAB_POP_SPEED: case RIAB_POP_RANDOM_SPATIAL:
-      case RIAB_POP_BVC: case RIAB_POP_OVC: break;
+      case RIAB_POP_BVC: break;
+      case RIAB_POP_OVC: {  // refused here, before the trajectory kernel is in flight, not by the launch of a chunk
+        const int limit = riab::ovc_object_limit();
+        if (limit >= 0 && q.n_objects > limit) return RIAB_ETOOBIG;
+        break;
+      }
       case RIAB_POP_FF:
         if (q.n_inputs <= 0 || q.n_inputs > RIAB_FF_MAX_INPUTS) return RIAB_EINVAL;
         for (int l = 0; l < q.n_inputs; ++l)

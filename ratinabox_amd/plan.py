@@ -294,7 +294,8 @@ class StepPlan:
     def step(self, n_steps=1, drift_velocity=None, drift_to_random_strength_ratio=1, dt=None):
         ag = self.agent
         if ag._plan is not self:
-            raise RuntimeError("this plan was closed (the agent was stepped eagerly or its history reset)")
+            raise RuntimeError("this plan was closed (the agent was stepped eagerly, its history reset or an object added to "
+                               "its environment): make a new one")
         dt = dt or ag.dt
         if self._task_env is not None:
             # actions land in the plan's persistent drift buffer: no per-step parameter resolution
