@@ -322,7 +322,11 @@ int riab_speed_cell(const RiabRateIO* io, float one_sigma_speed, riab_stream_t s
  *  inv_norm   device float32 [n]: 1 / cell_fr_norm (Neurons.py:1598-1604)
  *  egocentric needs io->hd_x / hd_y
  *  ray_out    device float32 [T][K][B] or NULL: the first-wall ray distances
- *             (diagnostic / parity of the ray stage) */
+ *             (diagnostic / parity of the ray stage; accepted with or without direction
+ *             windows).  A ray with no wall ahead reads 0 where the position stands on a wall
+ *             (l_a == 0, l_b on the segment) and wall 0's l_a otherwise, like the reference
+ * K > 256 needs more dynamic LDS than a launch gets without asking: RIAB_ETOOBIG, with nothing
+ * launched, where the runtime refuses it. */
 int riab_boundary_vector_cells(const RiabEnv* env, const RiabRateIO* io, const double* test_dirs,
                                const double* ray_rden, int32_t K, const float* cells, const float* vm_table,
                                const float* inv_norm, int32_t n, int32_t egocentric,

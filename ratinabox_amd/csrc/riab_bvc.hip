@@ -10,7 +10,9 @@
 //   stage A  all 8 waves cast the K rays of the tile against the walls in float64 (the
 //            nearest-wall decision is discrete; walls and the 1/denominator table are scalar loads),
 //            a ray and its opposite from one pair of wall intercepts where the table holds opposites,
-//            and leave d[k][lane] (fp32) in LDS;
+//            and leave d[k][lane] (fp32) in LDS.  A ray with no wall ahead reads 0 when the position stands ON a wall
+//            (l_a == 0 with l_b on the segment: the reference's preference 0 beats the -1 of every other wall), and
+//            wall 0's l_a otherwise (all preferences -1: argmax picks the first) — see `stands_on_wall`;
 //   stage B  wave w owns the 4-cell groups g = w (mod 8); per group the K-loop reads d[k][lane]
 //            (conflict-free ds_read_b32) and the wave-uniform angular table entry (scalar
 //            load), one fused exponent per term: exp2(-(a d - a mu)^2 + T[c][k]).
@@ -146,6 +148,25 @@ __global__ __launch_bounds__(512) void bvc_kernel(const BvcArgs a) {
     s_d[k * 64 + lane] = d;
     if (publish) st_agent(xrow + k * 64, d);
   };
+  // The miss path.  A ray that found no wall ahead (`best` still infinite) takes a second look over the walls: the
+  // reference's np.piecewise gives a wall with l_a == 0 and 0 <= l_b <= 1 — the position stands on it — the preference
+  // 0, which beats the -1 of every wall behind or off the ray, so the distance is that wall's l_a = 0 (whichever such
+  // wall comes first: the value is the same); only when there is none does argmax over all -1 pick wall 0.  The same
+  // l_a and l_b serve the opposite ray (l_a changes sign, 0 stays 0).  The hot (ray, wall) loops are untouched: every
+  // ray with a hit keeps its bits and its instruction count.  The box fast path cannot get here: it requires every
+  // live lane strictly inside the rectangle, where each ray crosses an edge's line ahead and no edge's l_a is 0.
+  auto stands_on_wall = [&](const double ux, const double uy, const int k) -> bool {
+    for (int w = 0; w < nw; ++w) {
+      const double ax = walls[4 * w], ay = walls[4 * w + 1];
+      const double sx = walls[4 * w + 2] - ax, sy = walls[4 * w + 3] - ay;
+      const double d0x = ax - px, d0y = ay - py;
+      const double rd = rden[k * nw + w];
+      const double la = (d0x * (-sy) + d0y * sx) * rd;
+      const double lb = ((-d0x) * (-uy) + (-d0y) * ux) * (-rd);
+      if (la == 0.0 && !(lb < 0.0) && !(lb > 1.0)) return true;
+    }
+    return false;
+  };
   // rays without a partner (see below), `count` of them: table index 0 for t = 0, t + off otherwise
   auto cast_single = [&](int count, int off) {
     for (int t0 = vw; t0 < count; t0 += nvw * KB) {
@@ -191,7 +212,8 @@ __global__ __launch_bounds__(512) void bvc_kernel(const BvcArgs a) {
       for (int i = 0; i < KB; ++i) {
         if (t0 + nvw * i < count) {
           const int k = kk[i];
-          const float d = (float)((best[i] < INFINITY) ? best[i] : fallback[i]);
+          const bool hit = best[i] < INFINITY;
+          const float d = (float)(hit ? best[i] : (stands_on_wall(ux[i], uy[i], k) ? 0.0 : fallback[i]));
           put(k, d);
           if (a.ray_out && live && (publish || part == 0)) a.ray_out[(t * K + k) * a.B + b] = d;
         }
@@ -264,8 +286,10 @@ __global__ __launch_bounds__(512) void bvc_kernel(const BvcArgs a) {
       for (int i = 0; i < KB; ++i) {
         if (q0 + nvw * i < np) {
           const int k = jj[i];
-          const float dp = (float)((bpos[i] < INFINITY) ? bpos[i] : fallback[i]);
-          const float dn = (float)((bneg[i] < INFINITY) ? bneg[i] : -fallback[i]);
+          const bool hit_p = bpos[i] < INFINITY, hit_n = bneg[i] < INFINITY;
+          const bool on = !(hit_p && hit_n) && stands_on_wall(ux[i], uy[i], k);  // (one look serves both directions)
+          const float dp = (float)(hit_p ? bpos[i] : (on ? 0.0 : fallback[i]));
+          const float dn = (float)(hit_n ? bneg[i] : (on ? 0.0 : -fallback[i]));
           put(k, dp);
           put(k + m, dn);
           if (a.ray_out && live && (publish || part == 0)) {
@@ -535,6 +559,15 @@ int riab::launch_bvc(const RiabEnv* env, const RiabRateIO* io, const double* tes
   int split = 1;
   while (split < 8 && tiles * split * 2 <= 512 && split * 2 * 8 <= n_groups) split *= 2;
   const dim3 grid((unsigned)tiles, (unsigned)split);
+  // K > 256 needs more than the 64 KiB of dynamic LDS a launch gets without asking; a runtime that will not give one
+  // workgroup that much is reported before anything is launched (and before the exchange counter moves)
+  if (lds > 64 * 1024) {
+    const void* const fn = egocentric ? (const void*)bvc_kernel<true> : (const void*)bvc_kernel<false>;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+      (void)hipGetLastError();
+      return RIAB_ETOOBIG;
+    }
+  }
   // The exchange: the tile's workgroups each cast every split-th batch of rays and read the others' — in a room of many
   // walls stage A is most of a one-row launch and was cast `split` times over.
   // Only where the whole grid is resident at once (three of these workgroups fit a compute unit; a workgroup whose partners
@@ -556,14 +589,7 @@ int riab::launch_bvc(const RiabEnv* env, const RiabRateIO* io, const double* tes
     a.xch_target = *xch_arrivals;
   }
   hipStream_t s = (hipStream_t)stream;
-  if (egocentric) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)bvc_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(bvc_kernel<true>, grid, dim3(512), lds, s, a);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)bvc_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(bvc_kernel<false>, grid, dim3(512), lds, s, a);
-  }
+  if (egocentric) hipLaunchKernelGGL(bvc_kernel<true>, grid, dim3(512), lds, s, a);
+  else hipLaunchKernelGGL(bvc_kernel<false>, grid, dim3(512), lds, s, a);
   return (int)hipGetLastError();
 }
