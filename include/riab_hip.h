@@ -30,7 +30,9 @@
 extern "C" {
 #endif
 
-#define RIAB_ABI_VERSION 11
+#define RIAB_ABI_VERSION 11    /* (the riab_history_* entry points were added at 11 without a bump: they are new exports
+                                * only; no struct, enum value or existing signature changed, so an older binding still
+                                * loads this library and a newer one finds a missing export at load time) */
 #define RIAB_MAX_WALLS 64     /* walls staged in LDS by the motion / BVC / line-of-sight kernels */
 #define RIAB_MAX_TEST_ANGLES 360
 #define RIAB_STATE_ROWS 12    /* rows of the agent state matrix, see below */
@@ -1100,6 +1102,54 @@ int riab_theta_sequence_rollout(const RiabEnv* env, const RiabMotion* motion, co
 
 /* ShiftAgent (SubAgent.py:466-478): pos_out [2][B] = lead position + lead head direction * shift_m. */
 int riab_shift_agent_position(const double* lead_state, int64_t B, double shift_m, double* pos_out, riab_stream_t stream);
+
+/* ---- Rate maps and occupancy from the device history ----------------------------------------------------------------
+ * The numbers behind Neurons.plot_rate_map(method="history") (Neurons.py:377-398, 479-490) and
+ * Agent.plot_position_heatmap (Agent.py:951-956), i.e. utils.bin_data_for_histogramming (utils.py:544-589) =
+ * np.histogram2d with explicit edges, computed where the history lives.  Every (step, agent) pair of the rows given is
+ * one sample; all agents pool into one map per cell.  Both stages ACCUMULATE into caller-owned buffers (zeroed by the
+ * caller before the first call), so a history spread over several chunks is handled chunk by chunk. */
+#define RIAB_RATEMAP_MAX_BINS 4096     /* nx * ny a grid may have (what one wave's LDS accumulator holds): 64 x 64 */
+#define RIAB_RATEMAP_DROPPED 0xFFFFu   /* the bin id of a sample outside the edges, with a NaN coordinate, or of a padding lane */
+#define RIAB_RATEMAP_FP32_RUN 0        /* the longest run of samples summed in fp32 before promotion to float64: 0 = the
+                                        * weighted sums are float64 from the first add on */
+
+/* Stage A, the bin of every sample (replaces the searchsorted inside np.histogram2d, utils.py:577-583).  hist: device
+ * float32 [T][RIAB_HIST_ROWS][B], rows RIAB_H_POS_X / _Y are read, widened to float64 and compared against the float64
+ * edges: k = searchsorted(edges, x, side="right") - 1, a value equal to the last edge goes to the last bin, k < 0, x >
+ * last edge or NaN in either coordinate drops the sample, and so does an agent index >= n_real (the padding lanes).
+ * edges_x [nx + 1], edges_y [ny + 1]: HOST float64, built by the caller as the reference builds them (np.arange(lo, hi +
+ * dx, dx)) and checked here before anything is launched; edges_dev: the same nx + 1 + ny + 1 values on the DEVICE, x
+ * first.  bin_ids: device uint16 [T][B], written: (ny - 1 - ky) * nx + kx — the reference's `heatmap.T[::-1, :]`
+ * orientation, first row the top of the room — or RIAB_RATEMAP_DROPPED.  counts: device int64 [ny][nx], the occupancy
+ * (Agent.py:956), ADDED to with integer atomics.  T = 0 launches nothing.
+ * RIAB_EINVAL: null pointers, n_real outside 0..B, fewer than two edges on an axis, edges that do not strictly increase;
+ * RIAB_EALIGN: B % 4 or misaligned pointers; RIAB_EUNSUPPORTED: nx * ny > RIAB_RATEMAP_MAX_BINS; RIAB_ETOOBIG: T * B / 4
+ * >= 2^31 - 1 (split the rows). */
+int riab_history_bin_index(const float* hist, int64_t T, int64_t B, int64_t n_real, const double* edges_x, int32_t nx,
+                           const double* edges_y, int32_t ny, const double* edges_dev, uint16_t* bin_ids,
+                           int64_t* counts, riab_stream_t stream);
+
+/* Doubles of workspace riab_history_rate_map needs for T rows of n cells x B agents on a grid of n_bins bins (the float64
+ * slabs of its time blocks), or a negative RIAB_E* code. */
+int64_t riab_history_rate_map_workspace(int64_t T, int32_t n, int64_t B, int32_t n_bins);
+
+/* Stage B, the weighted sums (replaces `np.histogram2d(..., weights=rate_timeseries_)`, utils.py:577-579, for every
+ * cell at once).  rows: device [T][n][B], float32 rates or — rows_are_spikes — uint8 spikes; bin_ids: device uint16
+ * [T][B] of the same steps (stage A); sums: device float64 [n][n_bins], ADDED to: sums[c][id] += rows[t][c][b] for every
+ * sample whose id < n_bins.  Each wave sums one cell over one block of steps in float64 in an LDS accumulator no other
+ * wave touches; the blocks' slabs (workspace: device float64, riab_history_rate_map_workspace doubles) are then added
+ * in block order.  The partition depends on (T, n, B, n_bins) alone: the same call gives the same bits.  Spike sums
+ * are integers and exact.  Errors as stage A; RIAB_EINVAL also for a workspace that is too small. */
+int riab_history_rate_map(const void* rows, int32_t rows_are_spikes, int64_t T, int32_t n, int64_t B,
+                          const uint16_t* bin_ids, int32_t n_bins, double* sums, double* workspace,
+                          int64_t workspace_doubles, riab_stream_t stream);
+
+/* The end of utils.bin_data_for_histogramming (utils.py:580-588): maps [n][n_bins] = sums, or with norm_by_bincount
+ * sums / counts with the counts of empty bins set to 1; zero_bins uint8 [n_bins] (or NULL) = 1 where no sample fell.
+ * sums and counts are left as they are, so accumulation can go on.  n = 0 writes zero_bins only. */
+int riab_history_rate_map_finish(const double* sums, const int64_t* counts, int32_t n, int32_t n_bins,
+                                 int32_t norm_by_bincount, double* maps, uint8_t* zero_bins, riab_stream_t stream);
 
 /* sizeof of the ABI's structs as compiled into the library (which: 0 RiabEnv, 1 RiabMotion, 2 RiabRateIO,
  * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at

@@ -1217,6 +1217,37 @@ class Agent:
         self._check_pipeline()
         return self._hist.stack()
 
+    def _history_rows(self, t_start=None, t_end=None):
+        """get_history_slice's (startid, endid) from the recorded times alone: no history row is copied to the host."""
+        self._sync_plan()
+        from ._ratemap import history_rows
+        return history_rows(self._times, self.dt, t_start, t_end)
+
+    def get_position_heatmap_tensor(self, dx=0.05, t_start=None, t_end=None):
+        """The occupancy counts behind plot_position_heatmap (reference Agent.py:951-956) on the device: int64 `(ny,
+        nx)`, oriented as utils.bin_data_for_histogramming returns it (first row = top of the room), every agent pooled
+        into one map.  Computed from the history chunks where they lie (csrc/riab_ratemap.hip, on the current stream).
+        `t_start` / `t_end` both None: the whole history, last row included, as the reference's call; otherwise the rows
+        of `get_history_slice(t_start, t_end)` (its `endid` excluded; `t_end=None` then ends at the last row, included)."""
+        from . import _ratemap
+        self._sync_plan()
+        self._settle_plan()
+        self._check_pipeline()
+        total = len(self._hist)
+        if total == 0:
+            raise ValueError("the agent has no history to bin")
+        start, stop = 0, total
+        if t_start is not None or t_end is not None:
+            start, stop = self._history_rows(t_start, t_end)
+            if t_end is None:
+                stop = total
+        return _ratemap.position_heatmap_tensor(self, 0.05 if dx is None else dx, start, stop)
+
+    def get_position_heatmap(self, dx=0.05, t_start=None, t_end=None):
+        """`get_position_heatmap_tensor` on the host: float64 `(ny, nx)` counts (exact integers), what the reference's
+        `utils.bin_data_for_histogramming(history["pos"], extent, dx)` returns."""
+        return self.get_position_heatmap_tensor(dx, t_start, t_end).cpu().numpy().astype(np.float64)
+
     def reset_history(self):
         if self._plan is not None:
             self._plan.close()

@@ -492,6 +492,54 @@ class Neurons:
         self.Agent._check_pipeline()
         return self._hist_fr.stack(), self._hist_sp.stack()
 
+    # ---- rate maps (reference Neurons.py:377-398, 479-490) ------------------------------------------
+    def get_rate_map_tensor(self, method="history", bin_size=0.05, t_start=None, t_end=None, spikes=False,
+                            norm_by_bincount=True, position_data_agent=None):
+        """The numbers behind plot_rate_map on the device: `(rate_maps float64 (n, ny, nx), zero_bins bool (ny, nx))`,
+        oriented as utils.bin_data_for_histogramming returns them (first row = top of the room).
+        method="history": for each cell and bin the mean (`norm_by_bincount`) or the sum of the recorded rates over the
+        samples — every (step, agent) pair of the rows `Agent.get_history_slice(t_start, t_end)` selects (`endid`
+        excluded: with `t_end=None` the last row is left out, as in the reference) — that fell in the bin; all agents
+        pool into one map.  `spikes=True` bins the spike history instead: counts, or counts per visit.
+        `position_data_agent`: bin against another agent's positions (same batch size, same number of recorded steps).
+        The history is read chunk by chunk where it lies (csrc/riab_ratemap.hip, current stream): nothing is stacked or
+        copied to the host.
+        method="groundtruth": get_state(evaluate_at="all") on the environment's discretised grid (Environment.dx, not
+        `bin_size`), `zero_bins` all False."""
+        Ag = self.Agent
+        if method == "groundtruth":
+            shape = tuple(Ag.Environment.discrete_coords.shape[:2])
+            fr = self.get_state_tensor(evaluate_at="all")[:, :self._last_P]
+            return (fr.to(torch.float64).reshape((int(self.n),) + shape).contiguous(),
+                    torch.zeros(shape, dtype=torch.bool, device=self._device))
+        if method != "history":
+            raise ValueError(f"method must be 'history' or 'groundtruth', got {method!r}")
+        from . import _ratemap
+        P = Ag if position_data_agent is None else position_data_agent
+        for A in ({id(Ag): Ag, id(P): P}).values():
+            A._sync_plan()
+            A._settle_plan()
+            A._check_pipeline()
+        hist = self._hist_sp if spikes else self._hist_fr
+        if len(hist) == 0:
+            what = "save_history and save_spikes" if spikes else "save_history"
+            raise ValueError(f"{self.name}: no recorded {'spikes' if spikes else 'rates'} to bin (update() with {what} on fills the history)")
+        if P is not Ag and (P._B != self._B or P._Bp != self._Bp or P._device != self._device):
+            raise ValueError("position_data_agent must have this population's batch size and device")
+        if len(P._hist) != len(hist):
+            raise ValueError(f"the position history has {len(P._hist)} rows, {self.name}'s has {len(hist)}: a rate map "
+                             "needs one position per recorded row")
+        start, stop = P._history_rows(t_start, t_end)
+        maps, zero, _counts = _ratemap.rate_map_tensors(P, hist, int(self.n), bin_size, start, stop, norm_by_bincount)
+        return maps, zero
+
+    def get_rate_map(self, method="history", bin_size=0.05, t_start=None, t_end=None, spikes=False,
+                     norm_by_bincount=True, position_data_agent=None):
+        """`get_rate_map_tensor` on the host: `(rate_maps (n, ny, nx) float64, zero_bins (ny, nx) bool)` NumPy arrays."""
+        maps, zero = self.get_rate_map_tensor(method, bin_size, t_start, t_end, spikes, norm_by_bincount,
+                                              position_data_agent)
+        return maps.cpu().numpy(), zero.cpu().numpy()
+
     def reset_history(self):
         if self.Agent._plan is not None:
             self.Agent._plan.close()  # (its open rows live in the chunks dropped here)

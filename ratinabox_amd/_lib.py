@@ -142,6 +142,7 @@ STEP1_SYNC_STRIDE, STEP1_SYNC_TAIL, STEP1_SYNC_TIMEOUTS = 64, 16, 0   # riab_hip
 STEP1_SYNC_FIRST_BAD, STEP1_SYNC_LAST_BAD, STEP1_SYNC_FATAL = 1, 2, 3
 STEP1_MAX_POPS = 4                                                      # csrc/riab_device.h RIAB_STEP1_MAX_POPS
 WALL_GRID_MAX = 16                                                      # riab_hip.h RIAB_WALL_GRID_MAX
+RATEMAP_MAX_BINS, RATEMAP_DROPPED, RATEMAP_FP32_RUN = 4096, 0xFFFF, 0     # riab_hip.h RIAB_RATEMAP_*
 CU_PROBE_WORDS = 4097                                                   # riab_hip.h RIAB_CU_PROBE_WORDS
 STEP1_MAIL_STRIDE = 1088                                                # riab_hip.h RIAB_STEP1_MAIL_STRIDE
 
@@ -218,6 +219,13 @@ PROTOTYPES = {
                                               C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32,
                                               C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "riab_shift_agent_position": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
+    "riab_history_bin_index": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "riab_history_rate_map_workspace": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64, C.c_int32]),
+    "riab_history_rate_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "riab_history_rate_map_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
     "riab_fill": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "riab_plan_create": (C.c_void_p, [C.POINTER(RiabEnv), C.POINTER(RiabMotion), C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -425,3 +425,89 @@ def simulate_(state: Tensor, hist: Tensor, rates: List[Tensor], spikes: List[Ten
         e = _L.RiabError(f"riab_simulate failed with code {rc}: {_L.strerror(rc)}")
         e.code = rc
         raise e
+
+
+# ---- rate maps and occupancy from the history: riab_history_* ------------------------------------------------------
+_EDGE_CACHE = {}
+
+
+def _edges(edges_x: Tensor, edges_y: Tensor, device):
+    """(host x, host y, device copy [nx + 1 + ny + 1]) of the two edge tensors: the library checks the host values
+    before it launches and the kernel reads the device copy (kept per content: a map is asked for again and again
+    on the same grid)."""
+    for e in (edges_x, edges_y):
+        if e.device.type != "cpu" or e.dtype != torch.float64 or e.dim() != 1 or not e.is_contiguous():
+            raise ValueError("edges must be contiguous float64 HOST tensors (np.arange(lo, hi + dx, dx))")
+    key = (edges_x.numpy().tobytes(), edges_y.numpy().tobytes(), str(device))
+    dev = _EDGE_CACHE.get(key)
+    if dev is None:
+        if len(_EDGE_CACHE) >= 16:
+            _EDGE_CACHE.clear()
+        dev = _EDGE_CACHE[key] = torch.cat((edges_x, edges_y)).to(device)
+    return dev
+
+
+@_register("history_bin_index(Tensor traj, Tensor edges_x, Tensor edges_y, int n_real, Tensor(a!) counts) -> Tensor",
+           lambda traj, edges_x, edges_y, n_real, counts: traj.new_empty((traj.shape[0], traj.shape[2]), dtype=torch.int16))
+def history_bin_index(traj: Tensor, edges_x: Tensor, edges_y: Tensor, n_real: int, counts: Tensor) -> Tensor:
+    """Stage A of a rate map (riab_history_bin_index): the bin of every (step, agent) sample of trajectory rows `traj`
+    float32 (T, 8, B) on the grid of the float64 HOST tensors edges_x (nx + 1,) / edges_y (ny + 1,) — np.histogram2d's
+    rule — for the first `n_real` agents of a row.  Returns the ids, (T, B) int16 holding the ABI's uint16 bits:
+    (ny - 1 - ky) * nx + kx, or -1 (= RIAB_RATEMAP_DROPPED) for a sample outside the grid, a NaN or a padding lane.
+    counts: int64 (ny, nx), the occupancy, ADDED to."""
+    if traj.dtype != torch.float32 or traj.dim() != 3 or traj.shape[1] != _L.HIST_ROWS or not traj.is_contiguous():
+        raise ValueError("traj must be a contiguous float32 tensor (T, 8, B)")
+    T, B = int(traj.shape[0]), int(traj.shape[2])
+    nx, ny = int(edges_x.shape[0]) - 1, int(edges_y.shape[0]) - 1
+    dev = _edges(edges_x, edges_y, traj.device)
+    if counts.dtype != torch.int64 or counts.numel() != max(nx, 0) * max(ny, 0) or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous int64 tensor (ny, nx)")
+    ids = torch.empty((T, B), dtype=torch.int16, device=traj.device)
+    _L.check(_L.lib.riab_history_bin_index(_L.ptr(traj), T, B, int(n_real), edges_x.data_ptr(), nx, edges_y.data_ptr(), ny,
+                                           _L.ptr(dev), _L.ptr(ids), _L.ptr(counts), _L.current_stream()),
+             "riab_history_bin_index")
+    return ids
+
+
+@_register("history_rate_map(Tensor rows, Tensor bin_ids, Tensor(a!) sums) -> ()", lambda rows, bin_ids, sums: None)
+def history_rate_map(rows: Tensor, bin_ids: Tensor, sums: Tensor) -> None:
+    """Stage B of a rate map (riab_history_rate_map), in place: sums[c].flat[id] += rows[t, c, b] for every sample whose
+    bin id is not dropped.  rows: float32 rates or uint8 spikes (T, n, B); bin_ids: int16 (T, B) from
+    `history_bin_index` on the same steps; sums: float64 (n, ny, nx), ADDED to (in float64 throughout; spike sums are
+    exact)."""
+    if rows.dtype not in (torch.float32, torch.uint8) or rows.dim() != 3 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous float32 (rates) or uint8 (spikes) tensor (T, n, B)")
+    T, n, B = (int(x) for x in rows.shape)
+    if bin_ids.dtype != torch.int16 or tuple(bin_ids.shape) != (T, B) or not bin_ids.is_contiguous():
+        raise ValueError("bin_ids must be a contiguous int16 tensor (T, B) of the same steps")
+    if sums.dtype != torch.float64 or sums.dim() < 2 or sums.shape[0] != n or not sums.is_contiguous():
+        raise ValueError("sums must be a contiguous float64 tensor (n, ny, nx)")
+    n_bins = int(sums.numel() // max(n, 1))
+    if n == 0:
+        return
+    need = int(_L.lib.riab_history_rate_map_workspace(T, n, B, n_bins))
+    if need < 0:
+        raise _L.RiabError(f"riab_history_rate_map_workspace failed with code {need}: {_L.strerror(need)}")
+    ws = torch.empty(max(need, 1), dtype=torch.float64, device=rows.device)
+    _L.check(_L.lib.riab_history_rate_map(_L.ptr(rows), 1 if rows.dtype == torch.uint8 else 0, T, n, B, _L.ptr(bin_ids),
+                                          n_bins, _L.ptr(sums), _L.ptr(ws), int(ws.numel()), _L.current_stream()),
+             "riab_history_rate_map")
+
+
+@_register("history_rate_map_finish(Tensor sums, Tensor counts, bool norm_by_bincount) -> (Tensor, Tensor)",
+           lambda sums, counts, norm_by_bincount: (sums.new_empty(sums.shape), counts.new_empty(counts.shape, dtype=torch.bool)))
+def history_rate_map_finish(sums: Tensor, counts: Tensor, norm_by_bincount: bool):
+    """The end of a rate map (riab_history_rate_map_finish): (maps float64 like sums — sums / counts with empty bins'
+    counts set to 1, or the sums —, zero_bins bool like counts: True where no sample fell)."""
+    if sums.dtype != torch.float64 or not sums.is_contiguous() or counts.dtype != torch.int64 or not counts.is_contiguous():
+        raise ValueError("sums must be contiguous float64 (n, ny, nx), counts contiguous int64 (ny, nx)")
+    n_bins = int(counts.numel())
+    n = int(sums.numel() // max(n_bins, 1))
+    if n * n_bins != sums.numel():
+        raise ValueError("sums must hold one map of counts' shape per cell")
+    maps = torch.empty_like(sums)
+    zero = torch.empty(counts.shape, dtype=torch.bool, device=counts.device)
+    _L.check(_L.lib.riab_history_rate_map_finish(_L.ptr(sums), _L.ptr(counts), n, n_bins, 1 if norm_by_bincount else 0,
+                                                 _L.ptr(maps), _L.ptr(zero), _L.current_stream()),
+             "riab_history_rate_map_finish")
+    return maps, zero

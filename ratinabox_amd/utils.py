@@ -421,3 +421,42 @@ def activate(x, activation="sigmoid", deriv=False, other_args={}):
     if name == "retanh":
         return g * (1 - np.tanh(x) ** 2) * (z > 0) if deriv else g * np.maximum(0, np.tanh(z))
     return g / (1 + np.exp(-z)) if deriv else g * np.log(1 + np.exp(z))
+
+
+# --------------------------------------------------------------------------- #
+# binning positions into maps (reference utils.py:544-589)
+# --------------------------------------------------------------------------- #
+def histogram_bin_edges(extent, dx):
+    """(edges_x, edges_y) of a map over `extent` = (left, right, bottom, top) with bins `dx` wide, float64, exactly as
+    the reference builds them (utils.py:575-576): np.arange(lo, hi + dx, dx).  The arange's rounding is part of the
+    definition: (0, 0.3) at dx 0.1 gets a last edge of 0.30000000000000004 and THREE bins, (-0.5, 0.5) at 0.05 a last
+    edge just below 0.5, so that a position on the far wall falls outside the map."""
+    if len(extent) != 4:
+        raise NotImplementedError("ratinabox_amd bins 2D data only")
+    dx = float(dx)
+    if not dx > 0:
+        raise ValueError("dx must be positive")
+    return (np.arange(float(extent[0]), float(extent[1]) + dx, dx), np.arange(float(extent[2]), float(extent[3]) + dx, dx))
+
+
+def bin_data_for_histogramming(data, extent, dx, weights=None, norm_by_bincount=False, return_zero_bins=False):
+    """The reference's utils.bin_data_for_histogramming (utils.py:544-589), 2D, on the host: `data` (N, 2) positions
+    binned by np.histogram2d on the edges of `histogram_bin_edges(extent, dx)`, each sample counting `weights[i]` (1
+    without weights); `norm_by_bincount` divides by the number of samples per bin (empty bins: by 1).  Returned as the
+    reference returns it, `heatmap.T[::-1, :]`: shape (ny, nx), first row the top of the room; with `return_zero_bins`
+    also the bool array of the bins no sample fell in.  This is the definition the device path
+    (Neurons.get_rate_map, Agent.get_position_heatmap) is held to."""
+    bins_x, bins_y = histogram_bin_edges(extent, dx)
+    data = np.asarray(data)
+    heatmap, _, _ = np.histogram2d(data[:, 0], data[:, 1], bins=[bins_x, bins_y], weights=weights)
+    zero_bins = None
+    if norm_by_bincount or return_zero_bins:
+        bincount, _, _ = np.histogram2d(data[:, 0], data[:, 1], bins=[bins_x, bins_y])
+        zero_bins = (bincount == 0)
+        if norm_by_bincount:
+            bincount[zero_bins] = 1
+            heatmap = heatmap / bincount
+    heatmap = heatmap.T[::-1, :]
+    if return_zero_bins:
+        return (heatmap, zero_bins.T[::-1, :])
+    return heatmap
