@@ -76,9 +76,11 @@ __device__ __forceinline__ u32x4 philox4x32_spikes(uint32_t c0, uint32_t c1, uin
 // (the one-launch closed-loop step: 16.8 MB of rates in 1.5 us, then the next step) gains 12 % from WT (9.67 -> 8.50 us
 // per step); a kernel that streams for milliseconds (rate_kernel_gated, 1024 rows) loses 9 % to it (1.45 -> 1.32 G
 // agent-steps/s: the L2 no longer combines the lanes' quads into full lines ahead of the memory channel).
+// RIAB_STORE_PLAIN: an ordinary store, for the kernels that choose between the two when they are compiled.
 #define RIAB_WT_BITS "sc1 nt"
 #define RIAB_STORE_NT 0
 #define RIAB_STORE_WT 1
+#define RIAB_STORE_PLAIN 2
 typedef float riab_v4f __attribute__((ext_vector_type(4)));
 template <int POLICY>
 __device__ __forceinline__ void store_stream(float* p, riab_v4f v) {
@@ -88,11 +90,13 @@ __device__ __forceinline__ void store_stream(float* p, riab_v4f v) {
   // made of their registers — tests/test_gpu_parity.py, spike shapes, and test_gpu_fused.py caught it.)
   if (POLICY == RIAB_STORE_WT)
     asm volatile("global_store_dwordx4 %0, %1, off " RIAB_WT_BITS "\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+  else if (POLICY == RIAB_STORE_PLAIN) *reinterpret_cast<riab_v4f*>(p) = v;
   else __builtin_nontemporal_store(v, reinterpret_cast<riab_v4f*>(p));
 }
 template <int POLICY>
 __device__ __forceinline__ void store_stream(uint32_t* p, uint32_t v) {
   if (POLICY == RIAB_STORE_WT) asm volatile("global_store_dword %0, %1, off " RIAB_WT_BITS ::"v"(p), "v"(v) : "memory");
+  else if (POLICY == RIAB_STORE_PLAIN) *p = v;
   else __builtin_nontemporal_store(v, p);
 }
 
@@ -177,6 +181,16 @@ __device__ __forceinline__ bool env_contains(const EnvShape& s, double px, doubl
                             : (px > s.e0 && px < s.e1 && py > s.e2 && py < s.e3);
   if (in && s.hole_mask) in = !polygon_contains_strict(px, py, s.hole_mask, edge);
   return in;
+}
+// The RiabRateIO view of a block of history rows (riab_hip.h RIAB_H_*): the position and head-direction rows of `rows`,
+// `B` agents wide, consecutive time rows `ld` floats apart (sets pos_x / pos_y / hd_x / hd_y, pos_ld and B).  Host side.
+static inline void hist_rows_io(RiabRateIO* io, const float* rows, int64_t B, int64_t ld) {
+  io->pos_x = rows + (int64_t)RIAB_H_POS_X * B;
+  io->pos_y = rows + (int64_t)RIAB_H_POS_Y * B;
+  io->hd_x = rows + (int64_t)RIAB_H_HD_X * B;
+  io->hd_y = rows + (int64_t)RIAB_H_HD_Y * B;
+  io->pos_ld = ld;
+  io->B = B;
 }
 // argument checks shared by the entry points
 static inline int check_env_shape(const RiabEnv* env) {

@@ -477,13 +477,8 @@ static int launch_population(RiabPlan* p, size_t i, const float* row, hipStream_
   RiabPopulation& q = p->pops[i];
   const int64_t B = p->B;
   RiabRateIO io = q.io;
-  io.pos_x = row + RIAB_H_POS_X * B;
-  io.pos_y = row + RIAB_H_POS_Y * B;
-  io.hd_x = row + RIAB_H_HD_X * B;
-  io.hd_y = row + RIAB_H_HD_Y * B;
-  io.pos_ld = B;
+  riab::hist_rows_io(&io, row, B, B);
   io.T = 1;
-  io.B = B;
   const int64_t r = p->pop_fill[i];
   io.rates = q.rates_base + r * (int64_t)q.n * B;
   io.spikes = q.spikes_base ? q.spikes_base + r * (int64_t)q.n * B : nullptr;

@@ -1,6 +1,6 @@
 #pragma once
 // The firing-rate functors of the store-bound populations (PlaceCells, GridCells, HeadDirectionCells / VelocityCells /
-// SpeedCell), the argument block of their kernels and the Poisson-spike epilogue.  Shared by the rate kernels
+// SpeedCell), the argument block of their kernels, the Poisson-spike epilogue and the cell-group body.  Shared by the rate kernels
 // (riab_rates.hip) and the one-launch closed-loop step (riab_step1.hip): the same inlined code on the same operands,
 // so a rate is the same bits whichever kernel evaluates it.
 #include "riab_device.h"
@@ -10,6 +10,15 @@ namespace riab {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
+
+// what the spike epilogue reads (spike_store)
+struct SpikeCtx {
+  uint8_t* spikes;       // the spike rows, laid out like the rates
+  const float* u_in;     // explicit uniforms (EXPLICIT_U)
+  float dt;
+  uint32_t k0, k1;       // Philox key (seed)
+  uint32_t tag;          // stream_tag(RIAB_TAG_SPIKES, pop_id)
+};
 
 struct RateArgs {
   const float* pos_x;
@@ -30,6 +39,7 @@ struct RateArgs {
   uint32_t group0;       // agent_id0 / 4
   int32_t n;
   int32_t cells_per_block;
+  __device__ __forceinline__ SpikeCtx spike_ctx() const { return SpikeCtx{spikes, u_in, dt, k0, k1, tag}; }
 };
 
 struct PosQuad {
@@ -51,13 +61,13 @@ template <class P_>
 __device__ __forceinline__ v4f finish_rate(v4f r, const P_&) { return r; }
 
 // post_scale: per-(cell, position) factor on the rate already scaled to [min_fr, max_fr], in front of finish_rate
-// (rate_kernel_wide / rate_kernel_generic).  Nothing for every functor but ThetaPlaceCell.
+// (RIAB_CELL_GROUP, rate_kernel_generic).  Nothing for every functor but ThetaPlaceCell.
 template <class Cell>
 __device__ __forceinline__ v4f post_scale(const Cell&, const float*, const typename Cell::Pos&, v4f r) { return r; }
 
 // ---- spike epilogue: Neurons.save_to_history (reference Neurons.py:681-687) -------------
 template <bool EXPLICIT_U, int POLICY = RIAB_STORE_NT>
-__device__ __forceinline__ void spike_store(const RateArgs& a, v4f r, int64_t off, uint32_t step, uint32_t c,
+__device__ __forceinline__ void spike_store(const SpikeCtx& a, v4f r, int64_t off, uint32_t step, uint32_t c,
                                             uint32_t group) {
   v4f u;
   if (EXPLICIT_U) {
@@ -170,13 +180,25 @@ struct PlaceCell {
     return r;
   }
   template <int D2>
-  __host__ PlaceCell<D2, GX> as() const {
-    PlaceCell<D2, GX> c;
-    c.tab = tab; c.scale = scale; c.half_scale = half_scale; c.top_hat_w2 = top_hat_w2;
-    c.walls = walls; c.n_internal = n_internal; c.e0 = e0; c.e1 = e1; c.e2 = e2; c.e3 = e3; c.shape = shape; c.lds = nullptr;
-    return c;
-  }
+  __host__ PlaceCell<D2, GX> as() const;
 };
+// The one spelling of a PlaceCell's fields: the host's make_place_cell (riab_rates.hip), as<>(), and the closed-loop step
+// (riab_step1.hip), which builds its functors on the device for rooms whose walls the rate does not look at (GX 0 / 3).
+template <int DESC, int GX>
+__host__ __device__ __forceinline__ PlaceCell<DESC, GX> place_cell(const float* tab, float scale, float half_scale, float top_hat_w2,
+                                                                   const double* walls = nullptr, int n_internal = 0,
+                                                                   const EnvShape& shape = EnvShape{}) {
+  PlaceCell<DESC, GX> c;
+  c.tab = tab; c.scale = scale; c.half_scale = half_scale; c.top_hat_w2 = top_hat_w2;
+  c.walls = walls; c.n_internal = n_internal;
+  c.e0 = shape.e0; c.e1 = shape.e1; c.e2 = shape.e2; c.e3 = shape.e3; c.shape = shape; c.lds = nullptr;
+  return c;
+}
+template <int DESC, int GX>
+template <int D2>
+__host__ PlaceCell<D2, GX> PlaceCell<DESC, GX>::as() const {
+  return place_cell<D2, GX>(tab, scale, half_scale, top_hat_w2, walls, n_internal, shape);
+}
 
 // ---- contribs.PhasePrecessingPlaceCells (reference contribs/PhasePrecessingPlaceCells.py:66-119) ----------
 // PlaceCell<DESC, GX> (the same inlined code on the same operands: the same bits as PlaceCells) times a von Mises of
@@ -373,5 +395,42 @@ struct HDCell {
 
 // VelocityCells: HDC_firingrates * speed_scale, AFTER the scaling to [min_fr, max_fr] (Neurons.py:2580-2582)
 __device__ __forceinline__ v4f finish_rate(v4f r, const HDCell<1>::Pos& P) { return r * P.speed; }
+
+// ---- one cell group: CPB consecutive cells for the lane's quad of agents -------------------------------------------
+// The body of rate_kernel_wide, rate_kernel_gated (riab_rates.hip) and the closed-loop step's s1_group (riab_step1.hip).
+// A macro, not a function: the compiler optimises a function on its own before it inlines it, and every kernel then comes
+// out with other code (instruction order, registers) than with the loop written in place; the kernels' code is pinned.
+//   Cell, CPB          the functor's type, cells per group
+//   cell, mine, P      the functor; the group's parameters, one float per lane (lane j * NP + i holds parameter i of cell
+//                      c0 + j), broadcast with v_readlane; the quad's positions as the functor wants them (Cell::Pos)
+//   c0, n              the group's first cell, the population's cells
+//   fr_scale, fr_min   [0,1] -> [min_fr, max_fr]
+//   rates, off, ld     the rates of cell c0 + j go to rates[off + j * ld]; `off` is an int64_t VARIABLE, advanced
+//   store              the lanes that write their values
+//   RATE_POLICY        store_stream's policy for the rates
+//   PHILOX, EXPLICIT   draw spikes from Philox uniforms / from explicit uniforms (conditions; wave-uniform where they are
+//                      not compile-time); SPIKE_POLICY: store_stream's policy for them; ctx: the SpikeCtx
+//   step, group        the spike stream's counter words beside the cell
+// post_scale is applied by all: it is the identity for every functor but ThetaPlaceCell.
+#define RIAB_CELL_GROUP(Cell, CPB, cell, mine, P, c0, n, fr_scale, fr_min, rates, off, ld, store, RATE_POLICY, PHILOX,       \
+                        EXPLICIT, SPIKE_POLICY, ctx, step, group)                                                         \
+  {                                                                                                                        \
+    static_assert(Cell::NP * (CPB) <= 64, "a cell group's parameters must fit one wave");                                  \
+    _Pragma("unroll") for (int j_ = 0; j_ < (CPB); ++j_) {                                                                 \
+      if ((c0) + j_ < (n)) { /* wave-uniform */                                                                            \
+        float p_[Cell::NP];                                                                                                \
+        _Pragma("unroll") for (int i_ = 0; i_ < Cell::NP; ++i_) p_[i_] = __builtin_bit_cast(                               \
+            float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine), j_ * Cell::NP + i_));                          \
+        v4f r_ = (cell).eval(p_, P);                                                                                       \
+        r_ = finish_rate(post_scale(cell, p_, P, r_ * (fr_scale) + (fr_min)), P); /* [0,1] -> [min_fr, max_fr] */          \
+        if (store) {                                                                                                       \
+          store_stream<(RATE_POLICY)>((rates) + (off), r_);                                                                \
+          if (PHILOX) spike_store<false, (SPIKE_POLICY)>(ctx, r_, off, step, (uint32_t)((c0) + j_), group);                \
+          if (EXPLICIT) spike_store<true, (SPIKE_POLICY)>(ctx, r_, off, step, (uint32_t)((c0) + j_), group);               \
+        }                                                                                                                  \
+        (off) += (ld);                                                                                                     \
+      }                                                                                                                    \
+    }                                                                                                                      \
+  }
 
 }  // namespace riab

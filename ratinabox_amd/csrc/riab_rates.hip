@@ -43,7 +43,6 @@ __global__ __launch_bounds__(256) void rate_kernel_wide(const RateArgs a, Cell c
   __shared__ double s_lds[Cell::LDS_DOUBLES];
   cell.stage(s_lds);
   constexpr int NP = Cell::NP;
-  static_assert(NP * CPB <= 64, "a cell group's parameters must fit one wave");
   const int lane = threadIdx.x & 63;
   const int c0 = blockIdx.y * CPB;
   const uint32_t t = blockIdx.z;
@@ -57,27 +56,12 @@ __global__ __launch_bounds__(256) void rate_kernel_wide(const RateArgs a, Cell c
   int64_t off = ((int64_t)t * a.n + c0) * a.B + 4 * (int64_t)qc;
   const uint32_t step = a.step0 + t;
   const uint32_t group = a.group0 + qc;
-#pragma unroll
-  for (int j = 0; j < CPB; ++j) {
-    if (c0 + j < a.n) {  // wave-uniform
-      float p[NP];
-#pragma unroll
-      for (int i = 0; i < NP; ++i)
-        p[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine), j * NP + i));
-      v4f r = cell.eval(p, P);
-      r = finish_rate(post_scale(cell, p, P, r * a.fr_scale + a.fr_min), P);  // [0,1] -> [min_fr, max_fr]
-      if (live) {
-        // (NT: a launch of ONE row — a population's update() inside a closed loop, kernels that need the result behind it:
-        // streamed and written through, nothing left for the dispatch's closing release to flush, riab_device.h; the
-        // many-row launches of an open-loop run keep ordinary stores: - 4 % at 1024 steps with nontemporal ones)
-        if (NT) store_stream<RIAB_STORE_WT>(a.rates + off, r);
-        else *reinterpret_cast<v4f*>(a.rates + off) = r;
-        if (SPK == 1) spike_store<false, NT ? RIAB_STORE_WT : RIAB_SPIKE_POLICY_WIDE>(a, r, off, step, (uint32_t)(c0 + j), group);
-        if (SPK == 2) spike_store<true, NT ? RIAB_STORE_WT : RIAB_SPIKE_POLICY_WIDE>(a, r, off, step, (uint32_t)(c0 + j), group);
-      }
-      off += a.B;
-    }
-  }
+  const SpikeCtx k = a.spike_ctx();
+  // (NT: a launch of ONE row — a population's update() inside a closed loop, kernels that need the result behind it:
+  // streamed and written through, nothing left for the dispatch's closing release to flush, riab_device.h; the
+  // many-row launches of an open-loop run keep ordinary stores: - 4 % at 1024 steps with nontemporal ones)
+  RIAB_CELL_GROUP(Cell, CPB, cell, mine, P, c0, a.n, a.fr_scale, a.fr_min, a.rates, off, a.B, live,
+                  NT ? RIAB_STORE_WT : RIAB_STORE_PLAIN, SPK == 1, SPK == 2, NT ? RIAB_STORE_WT : RIAB_SPIKE_POLICY_WIDE, k, step, group)
 }
 
 template <class Cell, int SPK>
@@ -113,8 +97,8 @@ __global__ __launch_bounds__(256) void rate_kernel_generic(const RateArgs a, Cel
       r = finish_rate(post_scale(cell, p, P, r * a.fr_scale + a.fr_min), P);
       if (live) {
         store_stream<RIAB_STORE_NT>(a.rates + off, r);
-        if (SPK == 1) spike_store<false>(a, r, off, step, (uint32_t)(cb + j), group);
-        if (SPK == 2) spike_store<true>(a, r, off, step, (uint32_t)(cb + j), group);
+        if (SPK == 1) spike_store<false>(a.spike_ctx(), r, off, step, (uint32_t)(cb + j), group);
+        if (SPK == 2) spike_store<true>(a.spike_ctx(), r, off, step, (uint32_t)(cb + j), group);
       }
       off += a.B;
     }
@@ -154,8 +138,8 @@ __global__ __launch_bounds__(256) void place_one_hot_kernel(const RateArgs a, Pl
     r = r * a.fr_scale + a.fr_min;
     store_stream<RIAB_STORE_NT>(a.rates + off, r);
     if (a.spikes) {
-      if (a.u_in) spike_store<true>(a, r, off, step, (uint32_t)c, group);
-      else spike_store<false>(a, r, off, step, (uint32_t)c, group);
+      if (a.u_in) spike_store<true>(a.spike_ctx(), r, off, step, (uint32_t)c, group);
+      else spike_store<false>(a.spike_ctx(), r, off, step, (uint32_t)c, group);
     }
     off += a.B;
   }
@@ -205,8 +189,8 @@ __global__ __launch_bounds__(256) void random_spatial_kernel(const RateArgs a, P
       const v4f r = acc[j] / den;  // no position in range of any anchor: 0/0 = NaN, like the reference
       store_stream<RIAB_STORE_NT>(a.rates + off, r);
       if (a.spikes) {
-        if (a.u_in) spike_store<true>(a, r, off, step, (uint32_t)(c0 + j), group);
-        else spike_store<false>(a, r, off, step, (uint32_t)(c0 + j), group);
+        if (a.u_in) spike_store<true>(a.spike_ctx(), r, off, step, (uint32_t)(c0 + j), group);
+        else spike_store<false>(a.spike_ctx(), r, off, step, (uint32_t)(c0 + j), group);
       }
       off += a.B;
     }
@@ -225,7 +209,7 @@ __global__ __launch_bounds__(256) void spikes_kernel(const RateArgs a) {
   int64_t off = ((int64_t)t * a.n + c0) * a.B + 4 * (int64_t)q;
   for (int c = c0; c < c1; ++c) {
     const v4f r = ldv4(a.rates + off);
-    spike_store<EXPLICIT_U>(a, r, off, a.step0 + t, (uint32_t)c, a.group0 + q);
+    spike_store<EXPLICIT_U>(a.spike_ctx(), r, off, a.step0 + t, (uint32_t)c, a.group0 + q);
     off += a.B;
   }
 }
@@ -354,7 +338,6 @@ __global__ __launch_bounds__(64 * WAVES) void rate_kernel_gated(const RateArgs a
   __shared__ double s_lds[Cell::LDS_DOUBLES];
   cell.stage(s_lds);
   constexpr int NP = Cell::NP;
-  static_assert(NP * CPB <= 64, "a cell group's parameters must fit one wave");
   static_assert(WAVES % 4 == 0, "four waves share a (1024 agents) x (CPB cells) tile");
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -394,24 +377,13 @@ __global__ __launch_bounds__(64 * WAVES) void rate_kernel_gated(const RateArgs a
   int64_t off = ((int64_t)t * a.n + c0) * a.B + 4 * (int64_t)q;
   const uint32_t step = a.step0 + t;
   const uint32_t group = a.group0 + q;
-#pragma unroll
-  for (int j = 0; j < CPB; ++j) {
-    if (c0 + j < a.n) {  // wave-uniform
-      float p[NP];
-#pragma unroll
-      for (int i = 0; i < NP; ++i)
-        p[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine), j * NP + i));
-      v4f r = cell.eval(p, P);
-      r = finish_rate(r * a.fr_scale + a.fr_min, P);
-      // Nontemporal: the rows stream past the L2 (nothing of them is read again by this call) and leave no dirty lines to
-      // write back when the kernel ends.  [MI355X] cfg 2 against ordinary stores: 20 steps: the kernel 57.9 -> 54.4 us,
-      // the region 102-104 -> 98-100 us; 64 / 256 steps + 5 / + 6 %.  (The ungated rate_kernel_wide is the other way
-      // round: - 4 % at 1024 steps, - 6 % at cfg 4 with nontemporal stores — RIAB_OPT_NT_STORES.)
-      store_stream<RIAB_STORE_NT>(a.rates + off, r);
-      if (SPK == 1) spike_store<false, RIAB_SPIKE_POLICY_GATED>(a, r, off, step, (uint32_t)(c0 + j), group);
-      off += a.B;
-    }
-  }
+  const SpikeCtx k = a.spike_ctx();
+  // Nontemporal: the rows stream past the L2 (nothing of them is read again by this call) and leave no dirty lines to
+  // write back when the kernel ends.  [MI355X] cfg 2 against ordinary stores: 20 steps: the kernel 57.9 -> 54.4 us,
+  // the region 102-104 -> 98-100 us; 64 / 256 steps + 5 / + 6 %.  (The ungated rate_kernel_wide is the other way
+  // round: - 4 % at 1024 steps, - 6 % at cfg 4 with nontemporal stores — RIAB_OPT_NT_STORES.)
+  RIAB_CELL_GROUP(Cell, CPB, cell, mine, P, c0, a.n, a.fr_scale, a.fr_min, a.rates, off, a.B, true, RIAB_STORE_NT, SPK == 1, false,
+                  RIAB_SPIKE_POLICY_GATED, k, step, group)
 #ifdef RIAB_PIPE_PROFILE
   if (c0 + CPB >= a.n && blockIdx.x + 1 == gridDim.x && (threadIdx.x & 255u) == 0) {  // the row's last workgroup is done
     drain_stores();
@@ -495,7 +467,8 @@ static int check_io(const RiabRateIO* io, int n, bool need_pos, bool need_hd) {
   return RIAB_OK;
 }
 
-static RateArgs make_args(const RiabRateIO* io, int n, dim3* grid) {
+// the kernels' argument block from an entry point's io (cells_per_block: generic_grid)
+static RateArgs make_args(const RiabRateIO* io, int n) {
   RateArgs a;
   a.pos_x = io->pos_x;
   a.pos_y = io->pos_y;
@@ -517,82 +490,117 @@ static RateArgs make_args(const RiabRateIO* io, int n, dim3* grid) {
   a.tag = riab::stream_tag(RIAB_TAG_SPIKES, io->pop_id);
   a.group0 = (uint32_t)(io->agent_id0 / 4);
   a.n = n;
-  const int64_t pblocks = (a.nquads + 255) / 256;
+  a.cells_per_block = 0;
+  return a;
+}
+
+// the grid of the kernels whose lanes are quads of agents flattened over all time rows (rate_kernel_generic and its
+// kin), and the chunk of cells a workgroup walks
+static dim3 generic_grid(RateArgs* a) {
+  const int64_t pblocks = (a->nquads + 255) / 256;
   // enough workgroups to fill 256 CUs x several waves, but keep >= 16 cells per lane so the
   // position load and index arithmetic amortise
   int chunks = (int)((4096 + pblocks - 1) / pblocks);
   if (chunks < 1) chunks = 1;
-  int cpb = (n + chunks - 1) / chunks;
+  int cpb = (a->n + chunks - 1) / chunks;
   cpb = ((cpb + 63) / 64) * 64;  // whole 64-cell groups (one table register per lane)
-  a.cells_per_block = cpb;
-  *grid = dim3((unsigned)pblocks, (unsigned)((n + cpb - 1) / cpb), 1);
-  return a;
+  a->cells_per_block = cpb;
+  return dim3((unsigned)pblocks, (unsigned)((a->n + cpb - 1) / cpb), 1);
 }
 
 template <class Cell>
 static int launch_rate(const RiabRateIO* io, int n, const Cell& cell, hipStream_t s) {
   constexpr int kCellsPerGroup = Cell::CPB;
-  dim3 grid;
-  const RateArgs a = make_args(io, n, &grid);
+  // the kernel is picked from a table: [spike mode: 0 none, 1 Philox uniforms, 2 explicit uniforms] ([NT] for the wide one)
+  using Kernel = void (*)(const RateArgs, Cell);
+  static constexpr Kernel kWide[6] = {
+      rate_kernel_wide<Cell, 0, kCellsPerGroup, false>, rate_kernel_wide<Cell, 0, kCellsPerGroup, true>,
+      rate_kernel_wide<Cell, 1, kCellsPerGroup, false>, rate_kernel_wide<Cell, 1, kCellsPerGroup, true>,
+      rate_kernel_wide<Cell, 2, kCellsPerGroup, false>, rate_kernel_wide<Cell, 2, kCellsPerGroup, true>};
+  static constexpr Kernel kGeneric[3] = {rate_kernel_generic<Cell, 0>, rate_kernel_generic<Cell, 1>, rate_kernel_generic<Cell, 2>};
+  RateArgs a = make_args(io, n);
+  const int spk = !io->spikes ? 0 : !io->u_in ? 1 : 2;
   if (a.qrow >= 256 && io->T <= 65535 && (n + kCellsPerGroup - 1) / kCellsPerGroup <= 65535) {
     // address-ordered wide kernel
     const dim3 g((unsigned)((a.qrow + 255) / 256), (unsigned)((n + kCellsPerGroup - 1) / kCellsPerGroup), (unsigned)io->T);
-    if (g_options[RIAB_OPT_NT_STORES] || io->T == 1) {  // (streamed, written-through stores: one-row launches; the option: A/B at any length)
-      if (!io->spikes) hipLaunchKernelGGL((rate_kernel_wide<Cell, 0, kCellsPerGroup, true>), g, dim3(256), 0, s, a, cell);
-      else if (!io->u_in) hipLaunchKernelGGL((rate_kernel_wide<Cell, 1, kCellsPerGroup, true>), g, dim3(256), 0, s, a, cell);
-      else hipLaunchKernelGGL((rate_kernel_wide<Cell, 2, kCellsPerGroup, true>), g, dim3(256), 0, s, a, cell);
-    } else if (!io->spikes) hipLaunchKernelGGL((rate_kernel_wide<Cell, 0, kCellsPerGroup, false>), g, dim3(256), 0, s, a, cell);
-    else if (!io->u_in) hipLaunchKernelGGL((rate_kernel_wide<Cell, 1, kCellsPerGroup, false>), g, dim3(256), 0, s, a, cell);
-    else hipLaunchKernelGGL((rate_kernel_wide<Cell, 2, kCellsPerGroup, false>), g, dim3(256), 0, s, a, cell);
+    const bool nt = g_options[RIAB_OPT_NT_STORES] || io->T == 1;  // (streamed, written-through stores: one-row launches; the option: A/B at any length)
+    hipLaunchKernelGGL(kWide[2 * spk + (nt ? 1 : 0)], g, dim3(256), 0, s, a, cell);
     return (int)hipGetLastError();
   }
-  if (!io->spikes) hipLaunchKernelGGL((rate_kernel_generic<Cell, 0>), grid, dim3(256), 0, s, a, cell);
-  else if (!io->u_in) hipLaunchKernelGGL((rate_kernel_generic<Cell, 1>), grid, dim3(256), 0, s, a, cell);
-  else hipLaunchKernelGGL((rate_kernel_generic<Cell, 2>), grid, dim3(256), 0, s, a, cell);
+  const dim3 grid = generic_grid(&a);
+  hipLaunchKernelGGL(kGeneric[spk], grid, dim3(256), 0, s, a, cell);
   return (int)hipGetLastError();
+}
+
+// ---- PlaceCell<DESC, GX> from what an entry point is given --------------------------------------------------------
+// A geometry the device code does not cover: RIAB_ETOOBIG / RIAB_EUNSUPPORTED, 0 otherwise.
+static int place_geometry_refused(const RiabEnv* env, int geometry) {
+  if (env->periodic) return geometry != RIAB_GEOM_EUCLIDEAN ? RIAB_EUNSUPPORTED : RIAB_OK;  // Neurons.py:908-921
+  if (geometry == RIAB_GEOM_EUCLIDEAN) return RIAB_OK;
+  if (env->n_walls - 4 > RIAB_MAX_WALLS) return RIAB_ETOOBIG;
+  if (geometry == RIAB_GEOM_GEODESIC && env->n_walls > 5) return RIAB_EUNSUPPORTED;  // Environment.py:736-739
+  return RIAB_OK;
+}
+// the entry points' check of (environment, geometry); an unknown geometry is visit_place_geometry's RIAB_EINVAL behind it
+static int place_geometry_check(const RiabEnv* env, int geometry) {
+  if (!env->periodic && geometry != RIAB_GEOM_EUCLIDEAN && env->n_walls > 4 && !env->walls) return RIAB_EINVAL;
+  return place_geometry_refused(env, geometry);
+}
+// f(std::integral_constant<int, GX>) for the functor's GX of (environment, geometry)
+template <class F>
+static int visit_place_geometry(const RiabEnv* env, int geometry, F&& f) {
+  if (env->periodic) return f(std::integral_constant<int, 3>{});
+  switch (geometry) {
+    case RIAB_GEOM_EUCLIDEAN: return f(std::integral_constant<int, 0>{});
+    case RIAB_GEOM_LINE_OF_SIGHT: return f(std::integral_constant<int, 1>{});
+    case RIAB_GEOM_GEODESIC: return f(std::integral_constant<int, 2>{});
+    default: return RIAB_EINVAL;
+  }
+}
+// the internal walls a PlaceCell<., GX> looks at (the geodesic distance: one)
+template <int GX>
+static int internal_walls(const RiabEnv* env) {
+  const int n_internal = env->n_walls > 4 ? env->n_walls - 4 : 0;
+  return (GX == 2 && n_internal > 1) ? 1 : n_internal;
+}
+template <int GX>
+static PlaceCell<RIAB_PC_GAUSSIAN, GX> make_place_cell(const RiabEnv* env, const float* table, float top_hat_width, int n_internal) {
+  return place_cell<RIAB_PC_GAUSSIAN, GX>(table, (float)env->scale, (float)(env->scale / 2), top_hat_width * top_hat_width,
+                                          env->walls, n_internal, make_env_shape(env));
+}
+// f(PlaceCell<desc, GX>) for the four descriptions that are a function of the distance to one centre; `otherwise` for
+// every other one (RIAB_PC_ONE_HOT among them: the callers differ in what they make of it)
+template <int GX, class F>
+static int visit_place_desc(int desc, const PlaceCell<RIAB_PC_GAUSSIAN, GX>& base, int otherwise, F&& f) {
+  switch (desc) {
+    case RIAB_PC_GAUSSIAN: return f(base);
+    case RIAB_PC_GAUSSIAN_THRESHOLD: return f(base.template as<RIAB_PC_GAUSSIAN_THRESHOLD>());
+    case RIAB_PC_DIFF_OF_GAUSSIANS: return f(base.template as<RIAB_PC_DIFF_OF_GAUSSIANS>());
+    case RIAB_PC_TOP_HAT: return f(base.template as<RIAB_PC_TOP_HAT>());
+    default: return otherwise;
+  }
+}
+template <class F>
+static int visit_grid_desc(int desc, const float* table, float f0, F&& f) {
+  if (desc == RIAB_GC_RECTIFIED) return f(GridCell<RIAB_GC_RECTIFIED>{table, f0, 1.0f / (1.0f - f0)});
+  if (desc == RIAB_GC_SHIFTED) return f(GridCell<RIAB_GC_SHIFTED>{table, f0, 1.0f});
+  return RIAB_EINVAL;
 }
 
 template <int GX>
 static int launch_place(const RiabRateIO* io, int n, int desc, const PlaceCell<RIAB_PC_GAUSSIAN, GX>& base,
                         hipStream_t s) {
-  switch (desc) {
-    case RIAB_PC_GAUSSIAN: return launch_rate(io, n, base, s);
-    case RIAB_PC_GAUSSIAN_THRESHOLD: return launch_rate(io, n, base.template as<RIAB_PC_GAUSSIAN_THRESHOLD>(), s);
-    case RIAB_PC_DIFF_OF_GAUSSIANS: return launch_rate(io, n, base.template as<RIAB_PC_DIFF_OF_GAUSSIANS>(), s);
-    case RIAB_PC_TOP_HAT: return launch_rate(io, n, base.template as<RIAB_PC_TOP_HAT>(), s);
-    case RIAB_PC_ONE_HOT: {
-      dim3 grid;
-      const RateArgs a = make_args(io, n, &grid);
-      grid.y = 1;
-      hipLaunchKernelGGL((place_one_hot_kernel<GX>), grid, dim3(256), 0, s, a, base);
-      return (int)hipGetLastError();
-    }
-    default: return RIAB_EINVAL;
+  if (desc == RIAB_PC_ONE_HOT) {  // its own kernel
+    RateArgs a = make_args(io, n);
+    dim3 grid = generic_grid(&a);
+    grid.y = 1;
+    hipLaunchKernelGGL((place_one_hot_kernel<GX>), grid, dim3(256), 0, s, a, base);
+    return (int)hipGetLastError();
   }
-}
-
-template <int GX>
-static int place_dispatch(const RiabEnv* env, const RiabRateIO* io, const float* cells, int n, int desc, float thw,
-                          hipStream_t s) {
-  PlaceCell<RIAB_PC_GAUSSIAN, GX> c;
-  c.tab = cells;
-  c.scale = (float)env->scale;
-  c.half_scale = (float)(env->scale / 2);
-  c.top_hat_w2 = thw * thw;
-  c.walls = env->walls;
-  c.n_internal = env->n_walls > 4 ? env->n_walls - 4 : 0;
-  if (GX == 2 && c.n_internal > 1) c.n_internal = 1;
-  c.e0 = env->extent[0]; c.e1 = env->extent[1]; c.e2 = env->extent[2]; c.e3 = env->extent[3];
-  c.shape = make_env_shape(env);
-  c.lds = nullptr;
-  return launch_place<GX>(io, n, desc, c, s);
+  return visit_place_desc(desc, base, RIAB_EINVAL, [&](const auto& c) { return launch_rate(io, n, c, s); });
 }
 
 // ---- launches of the flag-coupled rate stage (called by riab_simulate_fused, riab_simulate.hip) ----------------
-// start / stop events of the one rate_kernel_gated launch of a launch_rate_stream call (kernel-level timing through
-// hipExtLaunchKernel; per thread, set and cleared by launch_rate_stream)
-static thread_local hipEvent_t t_stream_ev0 = nullptr, t_stream_ev1 = nullptr;
-
 // 25 us in ticks of the device's constant clock (s_memrealtime): how soon after the trajectory kernel's end a rate
 // stage that shared its hardware queue begins (barrier + [one-wave gate + barrier] + dispatch: 4-12 us [MI355X])
 static uint32_t serial_gap_ticks() {
@@ -607,32 +615,47 @@ static uint32_t serial_gap_ticks() {
 }
 
 int traj_kernel_regs();   // riab_agent.hip
-static thread_local bool t_stream_reserve = false;  // launch the reserving (twelve-wave) shape: set by launch_rate_stream
+// one rate_kernel_gated launch, as launch_rate_stream describes it to launch_stream_cell
+struct StreamLaunch {
+  StreamArgs st;
+  hipEvent_t ev0, ev1;  // start / stop events of the launch (kernel-level timing through hipExtLaunchKernel), or null
+  int T;
+  bool spikes;
+  bool reserve;         // launch the reserving (twelve-wave) shape
+  bool dry_run;
+  hipStream_t s;
+};
 
 template <class Cell>
-static int launch_stream_cell(const RateArgs& a, const Cell& cell, const StreamArgs& st_in, int T, bool spikes, bool dry_run,
-                              hipStream_t s) {
-  const hipEvent_t ev0 = t_stream_ev0, ev1 = t_stream_ev1;
+static int launch_stream_cell(const RateArgs& a, const Cell& cell, const StreamLaunch& L) {
   // Twice the wide kernel's cells per wave where the group's parameters still fit one wave (PlaceCells: 8): a gated
   // wave pays two dependent round trips to memory (progress words, then the write-through positions) before its
   // first store, so it should bring more stores with it.  [MI355X] cfg 2: K = 20 +1.5 %, K = 128 +4 %; x4: the same.
   constexpr int CPB = (Cell::NP * 2 * Cell::CPB <= 64) ? 2 * Cell::CPB : Cell::CPB;
+  // the kernel's variants: [reserving shape][spikes][LONG] — one index for the table, the register check and the
+  // first-launch flags
+  using Kernel = void (*)(const RateArgs, Cell, const StreamArgs);
+  static constexpr Kernel kGated[8] = {
+      rate_kernel_gated<Cell, 0, CPB, false, 4>,  rate_kernel_gated<Cell, 0, CPB, true, 4>,
+      rate_kernel_gated<Cell, 1, CPB, false, 4>,  rate_kernel_gated<Cell, 1, CPB, true, 4>,
+      rate_kernel_gated<Cell, 0, CPB, false, 12>, rate_kernel_gated<Cell, 0, CPB, true, 12>,
+      rate_kernel_gated<Cell, 1, CPB, false, 12>, rate_kernel_gated<Cell, 1, CPB, true, 12>};
+  const int T = L.T;
   const int64_t groups = (a.n + CPB - 1) / CPB;
   if (T > 65535 || groups > 65535) return RIAB_ETOOBIG;  // grid y / z limits: the caller splits longer runs
-  const bool reserve = t_stream_reserve;
-  const bool lng = T > 256;
-  if (reserve) {
+  const bool reserve = L.reserve;
+  const int variant = (reserve ? 4 : 0) + (L.spikes ? 2 : 0) + (T > 256 ? 1 : 0);
+  if (reserve) {  // (short calls of one population from an idle stream: no spikes-with-LONG zoo needed, but keep all four)
     // The reserving shape keeps its promise (riab_hip.h "Residency") only while wave slots are the ONLY resource it can
     // exhaust: two twelve-wave workgroups per compute unit are six waves per SIMD, and next to them a trajectory
     // workgroup's 224 registers per lane must still fit the SIMD's 512: at most 48 per lane here (the euclidean /
     // periodic place, grid and head-direction kernels hold 32-40; the line-of-sight and geodesic ones 88-96, where one
     // more register class would fit two workgroups and leave too little).  Asked of the code object once per kernel.
-    static int regs[4] = {0, 0, 0, 0};
-    int& r = regs[(spikes ? 2 : 0) + (lng ? 1 : 0)];
+    static int regs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int& r = regs[variant];
     if (r == 0) {
       hipFuncAttributes attr;
-      const void* f = spikes ? (lng ? (const void*)rate_kernel_gated<Cell, 1, CPB, true, 12> : (const void*)rate_kernel_gated<Cell, 1, CPB, false, 12>)
-                             : (lng ? (const void*)rate_kernel_gated<Cell, 0, CPB, true, 12> : (const void*)rate_kernel_gated<Cell, 0, CPB, false, 12>);
+      const void* f = (const void*)kGated[variant];
       r = (hipFuncGetAttributes(&attr, f) == hipSuccess && attr.numRegs > 0) ? attr.numRegs : 1 << 20;
       // (... and LDS: two of these workgroups next to a trajectory workgroup's 80 KB must fit the compute unit's 160 KB; the
       // kernels that are offered the shape declare 8 bytes — anything beyond a few KB is refused like too many registers)
@@ -643,60 +666,34 @@ static int launch_stream_cell(const RateArgs& a, const Cell& cell, const StreamA
     // trajectory kernel's 224 that is r <= 48)
     if (6 * ((r + 7) / 8 * 8) + traj_kernel_regs() > 512) return RIAB_EUNSUPPORTED;  // (the caller falls back to the started gate)
   }
-  if (dry_run) return RIAB_OK;  // (every argument check is above: nothing is launched)
+  if (L.dry_run) return RIAB_OK;  // (every argument check is above: nothing is launched)
   // (a kernel's FIRST launch in a process resolves its code object on the host — tens of microseconds in which a short
   // trajectory kernel finishes: that call says nothing about hardware queues, it is not examined)
   static bool launched[8] = {false, false, false, false, false, false, false, false};
-  bool& seen = launched[(reserve ? 4 : 0) + (spikes ? 2 : 0) + (lng ? 1 : 0)];
-  StreamArgs st = st_in;
+  bool& seen = launched[variant];
+  StreamArgs st = L.st;
   if (!seen) st.serial_rows = 0u;
   seen = true;
   const dim3 grid((unsigned)((a.qrow + 255) / 256), (unsigned)(reserve ? (groups + 2) / 3 : groups), (unsigned)T);
   const dim3 block(reserve ? 768 : 256);
-  auto go = [&](auto kernel) {
-    if (ev0 || ev1) hipExtLaunchKernelGGL(kernel, grid, block, 0, s, ev0, ev1, 0u, a, cell, st);
-    else hipLaunchKernelGGL(kernel, grid, block, 0, s, a, cell, st);
-  };
-  if (reserve) {  // (short calls of one population from an idle stream: no spikes-with-LONG zoo needed, but keep all four)
-    if (spikes) {
-      if (lng) go(rate_kernel_gated<Cell, 1, CPB, true, 12>);
-      else go(rate_kernel_gated<Cell, 1, CPB, false, 12>);
-    } else {
-      if (lng) go(rate_kernel_gated<Cell, 0, CPB, true, 12>);
-      else go(rate_kernel_gated<Cell, 0, CPB, false, 12>);
-    }
-  } else if (spikes) {
-    if (lng) go(rate_kernel_gated<Cell, 1, CPB, true, 4>);
-    else go(rate_kernel_gated<Cell, 1, CPB, false, 4>);
-  } else {
-    if (lng) go(rate_kernel_gated<Cell, 0, CPB, true, 4>);
-    else go(rate_kernel_gated<Cell, 0, CPB, false, 4>);
-  }
+  if (L.ev0 || L.ev1) hipExtLaunchKernelGGL(kGated[variant], grid, block, 0, L.s, L.ev0, L.ev1, 0u, a, cell, st);
+  else hipLaunchKernelGGL(kGated[variant], grid, block, 0, L.s, a, cell, st);
   return (int)hipGetLastError();
 }
 
-template <int GX>
-static int launch_stream_place(const RiabEnv* env, const RiabPopulation* pop, const RateArgs& a, const StreamArgs& st, int T,
-                               bool spikes, bool dry_run, hipStream_t s) {
-  PlaceCell<RIAB_PC_GAUSSIAN, GX> c;
-  c.tab = pop->table;
-  c.scale = (float)env->scale;
-  c.half_scale = (float)(env->scale / 2);
-  c.top_hat_w2 = pop->top_hat_width * pop->top_hat_width;
-  c.walls = env->walls;
-  c.n_internal = env->n_walls > 4 ? env->n_walls - 4 : 0;
-  if (GX == 2 && c.n_internal > 1) c.n_internal = 1;
-  c.e0 = env->extent[0]; c.e1 = env->extent[1]; c.e2 = env->extent[2]; c.e3 = env->extent[3];
-  c.shape = make_env_shape(env);
-  c.lds = nullptr;
-  switch (pop->description) {
-    case RIAB_PC_GAUSSIAN: return launch_stream_cell(a, c, st, T, spikes, dry_run, s);
-    case RIAB_PC_GAUSSIAN_THRESHOLD:
-      return launch_stream_cell(a, c.template as<RIAB_PC_GAUSSIAN_THRESHOLD>(), st, T, spikes, dry_run, s);
-    case RIAB_PC_DIFF_OF_GAUSSIANS:
-      return launch_stream_cell(a, c.template as<RIAB_PC_DIFF_OF_GAUSSIANS>(), st, T, spikes, dry_run, s);
-    case RIAB_PC_TOP_HAT: return launch_stream_cell(a, c.template as<RIAB_PC_TOP_HAT>(), st, T, spikes, dry_run, s);
-    default: return RIAB_EUNSUPPORTED;  // one_hot scans every cell per position: not a streaming shape
+// f(functor) for a population of the streamed kinds (place, grid, head direction)
+template <class F>
+static int visit_stream_cell(const RiabEnv* env, const RiabPopulation* pop, F&& f) {
+  switch (pop->kind) {
+    case RIAB_POP_PLACE:
+      return visit_place_geometry(env, pop->geometry, [&](auto gx) {
+        // (RIAB_EUNSUPPORTED: one_hot scans every cell per position: not a streaming shape)
+        return visit_place_desc(pop->description, make_place_cell<decltype(gx)::value>(env, pop->table, pop->top_hat_width, internal_walls<decltype(gx)::value>(env)),
+                                RIAB_EUNSUPPORTED, f);
+      });
+    case RIAB_POP_GRID: return visit_grid_desc(pop->description, pop->table, pop->f0, f);
+    case RIAB_POP_HDC: return f(HDCell<0>{pop->table, 0.0f, nullptr, nullptr});
+    default: return RIAB_EUNSUPPORTED;
   }
 }
 
@@ -707,9 +704,7 @@ int stream_supported(const RiabEnv* env, const RiabPopulation* pop, int64_t B) {
   switch (pop->kind) {
     case RIAB_POP_PLACE:
       if (pop->description == RIAB_PC_ONE_HOT) return RIAB_EUNSUPPORTED;
-      if (env->periodic && pop->geometry != RIAB_GEOM_EUCLIDEAN) return RIAB_EUNSUPPORTED;
-      if (pop->geometry != RIAB_GEOM_EUCLIDEAN && env->n_walls - 4 > RIAB_MAX_WALLS) return RIAB_EUNSUPPORTED;
-      if (pop->geometry == RIAB_GEOM_GEODESIC && env->n_walls > 5) return RIAB_EUNSUPPORTED;
+      if (place_geometry_refused(env, pop->geometry)) return RIAB_EUNSUPPORTED;
       return pop->table ? RIAB_OK : RIAB_EINVAL;
     case RIAB_POP_GRID:
     case RIAB_POP_HDC: return pop->table ? RIAB_OK : RIAB_EINVAL;
@@ -721,36 +716,21 @@ int launch_rate_stream(const RiabEnv* env, const RiabPopulation* pop, const floa
                        uint64_t seed, uint64_t step0, int64_t agent_id0, uint32_t* ctrl, uint32_t spin_limit, bool stamps,
                        hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, bool dry_run, bool reserve,
                        uint32_t serial_rows) {
-  struct EventScope {
-    EventScope(hipEvent_t a, hipEvent_t b, bool r) { t_stream_ev0 = a; t_stream_ev1 = b; t_stream_reserve = r; }
-    ~EventScope() { t_stream_ev0 = t_stream_ev1 = nullptr; t_stream_reserve = false; }
-  } scope(ev_start, ev_stop, reserve);
   int rc = stream_supported(env, pop, B);
   if (rc) return rc;
   if (!hist || !ctrl || !pop->rates_base || T <= 0 || pop->capacity_rows < T || agent_id0 % 4) return RIAB_EINVAL;
   if ((((uintptr_t)hist | (uintptr_t)pop->rates_base) & 15) || ((uintptr_t)pop->spikes_base & 3)) return RIAB_EALIGN;
-  RateArgs a;
-  a.pos_x = hist + (int64_t)RIAB_H_POS_X * B;
-  a.pos_y = hist + (int64_t)RIAB_H_POS_Y * B;
-  a.hd_x = hist + (int64_t)RIAB_H_HD_X * B;
-  a.hd_y = hist + (int64_t)RIAB_H_HD_Y * B;
-  a.pos_ld = (int64_t)RIAB_HIST_ROWS * B;
-  a.qrow = B / 4;
-  a.nquads = (int64_t)T * a.qrow;
-  a.B = B;
-  a.rates = pop->rates_base;
-  a.spikes = pop->spikes_base;
-  a.u_in = nullptr;
-  a.dt = dt;
-  a.fr_scale = pop->io.max_fr - pop->io.min_fr;
-  a.fr_min = pop->io.min_fr;
-  a.k0 = (uint32_t)seed;
-  a.k1 = (uint32_t)(seed >> 32);
-  a.step0 = (uint32_t)(step0 + 1);  // Neurons.update after the (step0 + t + 1)-th Agent.update
-  a.tag = riab::stream_tag(RIAB_TAG_SPIKES, pop->io.pop_id);
-  a.group0 = (uint32_t)(agent_id0 / 4);
-  a.n = pop->n;
-  a.cells_per_block = 0;
+  RiabRateIO io = pop->io;
+  hist_rows_io(&io, hist, B, (int64_t)RIAB_HIST_ROWS * B);
+  io.T = T;
+  io.rates = pop->rates_base;
+  io.spikes = pop->spikes_base;
+  io.u_in = nullptr;
+  io.dt = dt;
+  io.seed = seed;
+  io.step0 = step0 + 1;  // Neurons.update after the (step0 + t + 1)-th Agent.update
+  io.agent_id0 = agent_id0;
+  const RateArgs a = make_args(&io, pop->n);
   StreamArgs st;
   st.ctrl = ctrl;
   st.step_base = (uint32_t)step0;
@@ -759,32 +739,8 @@ int launch_rate_stream(const RiabEnv* env, const RiabPopulation* pop, const floa
   st.sleep_max = (uint32_t)g_options[RIAB_OPT_POLL_SLEEP];
   st.serial_rows = serial_rows;
   st.serial_gap = serial_gap_ticks();
-  const bool spikes = pop->spikes_base != nullptr;
-  switch (pop->kind) {
-    case RIAB_POP_PLACE:
-      if (env->periodic) return launch_stream_place<3>(env, pop, a, st, T, spikes, dry_run, s);
-      switch (pop->geometry) {
-        case RIAB_GEOM_EUCLIDEAN: return launch_stream_place<0>(env, pop, a, st, T, spikes, dry_run, s);
-        case RIAB_GEOM_LINE_OF_SIGHT: return launch_stream_place<1>(env, pop, a, st, T, spikes, dry_run, s);
-        case RIAB_GEOM_GEODESIC: return launch_stream_place<2>(env, pop, a, st, T, spikes, dry_run, s);
-        default: return RIAB_EINVAL;
-      }
-    case RIAB_POP_GRID:
-      if (pop->description == RIAB_GC_RECTIFIED) {
-        GridCell<RIAB_GC_RECTIFIED> c{pop->table, pop->f0, 1.0f / (1.0f - pop->f0)};
-        return launch_stream_cell(a, c, st, T, spikes, dry_run, s);
-      }
-      if (pop->description == RIAB_GC_SHIFTED) {
-        GridCell<RIAB_GC_SHIFTED> c{pop->table, pop->f0, 1.0f};
-        return launch_stream_cell(a, c, st, T, spikes, dry_run, s);
-      }
-      return RIAB_EINVAL;
-    case RIAB_POP_HDC: {
-      HDCell<0> c{pop->table, 0.0f, nullptr, nullptr};
-      return launch_stream_cell(a, c, st, T, spikes, dry_run, s);
-    }
-    default: return RIAB_EUNSUPPORTED;
-  }
+  const StreamLaunch L{st, ev_start, ev_stop, T, pop->spikes_base != nullptr, reserve, dry_run, s};
+  return visit_stream_cell(env, pop, [&](const auto& c) { return launch_stream_cell(a, c, L); });
 }
 
 int launch_stream_open(uint32_t* ctrl, uint32_t n_traj, uint32_t step_base, hipStream_t s) {
@@ -811,22 +767,12 @@ extern "C" int riab_place_cells(const RiabEnv* env, const RiabRateIO* io, const 
   if (!env || !cells) return RIAB_EINVAL;
   const int rc = check_io(io, n, true, false);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (env->periodic) {
-    if (geometry != RIAB_GEOM_EUCLIDEAN) return RIAB_EUNSUPPORTED;  // Neurons.py:908-921
-    return place_dispatch<3>(env, io, cells, n, description, top_hat_width, s);
-  }
-  if (geometry != RIAB_GEOM_EUCLIDEAN) {
-    if (env->n_walls > 4 && !env->walls) return RIAB_EINVAL;
-    if (env->n_walls - 4 > RIAB_MAX_WALLS) return RIAB_ETOOBIG;
-    if (geometry == RIAB_GEOM_GEODESIC && env->n_walls > 5) return RIAB_EUNSUPPORTED;  // Environment.py:736-739
-  }
-  switch (geometry) {
-    case RIAB_GEOM_EUCLIDEAN: return place_dispatch<0>(env, io, cells, n, description, top_hat_width, s);
-    case RIAB_GEOM_LINE_OF_SIGHT: return place_dispatch<1>(env, io, cells, n, description, top_hat_width, s);
-    case RIAB_GEOM_GEODESIC: return place_dispatch<2>(env, io, cells, n, description, top_hat_width, s);
-    default: return RIAB_EINVAL;
-  }
+  const int bad = place_geometry_check(env, geometry);
+  if (bad) return bad;
+  return visit_place_geometry(env, geometry, [&](auto gx) {
+    constexpr int GX = decltype(gx)::value;
+    return launch_place<GX>(io, n, description, make_place_cell<GX>(env, cells, top_hat_width, internal_walls<GX>(env)), (hipStream_t)stream);
+  });
 }
 
 // exp(kappa) / I0(kappa), float64: the power series of I0 has positive terms only (no cancellation at any kappa it
@@ -860,25 +806,12 @@ static int launch_theta(const RiabRateIO* io, int n, const PlaceCell<DESC, GX>& 
 template <int GX>
 static int theta_place_dispatch(const RiabEnv* env, const RiabRateIO* io, const float* cells, int n, int desc, float thw,
                                 double kappa, double theta_rev, const double* vel_x, const double* vel_y, hipStream_t s) {
-  PlaceCell<RIAB_PC_GAUSSIAN, GX> c;
-  c.tab = cells;
-  c.scale = (float)env->scale;
-  c.half_scale = (float)(env->scale / 2);
-  c.top_hat_w2 = thw * thw;
-  c.walls = env->walls;
-  c.n_internal = 0;
-  c.e0 = env->extent[0]; c.e1 = env->extent[1]; c.e2 = env->extent[2]; c.e3 = env->extent[3];
-  c.shape = make_env_shape(env);
-  c.lds = nullptr;
+  const PlaceCell<RIAB_PC_GAUSSIAN, GX> c = make_place_cell<GX>(env, cells, thw, 0);  // (euclidean: no wall is looked at)
   const float phase0 = (float)(0.5 - theta_rev), k2 = (float)(kappa * 1.4426950408889634), norm = (float)von_mises_peak(kappa);
-  auto go = [&](auto base) { return launch_theta(io, n, base, ThetaMod{cells, vel_x, vel_y, phase0, k2, norm}, s); };
-  switch (desc) {
-    case RIAB_PC_GAUSSIAN: return go(c);
-    case RIAB_PC_GAUSSIAN_THRESHOLD: return go(c.template as<RIAB_PC_GAUSSIAN_THRESHOLD>());
-    case RIAB_PC_DIFF_OF_GAUSSIANS: return go(c.template as<RIAB_PC_DIFF_OF_GAUSSIANS>());
-    case RIAB_PC_TOP_HAT: return go(c.template as<RIAB_PC_TOP_HAT>());
-    default: return RIAB_EINVAL;  // one_hot has no width (contribs/PhasePrecessingPlaceCells.py:58-63)
-  }
+  // (RIAB_EINVAL: one_hot has no width, contribs/PhasePrecessingPlaceCells.py:58-63)
+  return visit_place_desc(desc, c, RIAB_EINVAL, [&](const auto& base) {
+    return launch_theta(io, n, base, ThetaMod{cells, vel_x, vel_y, phase0, k2, norm}, s);
+  });
 }
 
 extern "C" int riab_phase_precessing_place_cells(const RiabEnv* env, const RiabRateIO* io, const float* cells, int32_t n,
@@ -906,19 +839,9 @@ extern "C" int riab_phase_precessing_place_cells(const RiabEnv* env, const RiabR
 template <int GX>
 static int random_spatial_dispatch(const RiabEnv* env, const RiabRateIO* io, const float* anchors, int M,
                                    const float* targets, int n, hipStream_t s) {
-  PlaceCell<RIAB_PC_GAUSSIAN, GX> c;
-  c.tab = anchors;
-  c.scale = (float)env->scale;
-  c.half_scale = (float)(env->scale / 2);
-  c.top_hat_w2 = 0.0f;
-  c.walls = env->walls;
-  c.n_internal = env->n_walls > 4 ? env->n_walls - 4 : 0;
-  if (GX == 2 && c.n_internal > 1) c.n_internal = 1;
-  c.e0 = env->extent[0]; c.e1 = env->extent[1]; c.e2 = env->extent[2]; c.e3 = env->extent[3];
-  c.shape = make_env_shape(env);
-  c.lds = nullptr;
-  dim3 grid;
-  RateArgs a = make_args(io, n, &grid);
+  const PlaceCell<RIAB_PC_GAUSSIAN, GX> c = make_place_cell<GX>(env, anchors, 0.0f, internal_walls<GX>(env));
+  RateArgs a = make_args(io, n);
+  dim3 grid = generic_grid(&a);
   a.fr_scale = 1.0f;  // the targets already lie in [min_fr, max_fr] (Neurons.py:2911-2912)
   a.fr_min = 0.0f;
   grid.y = (unsigned)((n + RS_CH - 1) / RS_CH);
@@ -932,22 +855,11 @@ extern "C" int riab_random_spatial_neurons(const RiabEnv* env, const RiabRateIO*
   const int rc = check_io(io, n, true, false);
   if (rc) return rc;
   if ((n + RS_CH - 1) / RS_CH > 65535) return RIAB_ETOOBIG;
-  hipStream_t s = (hipStream_t)stream;
-  if (env->periodic) {
-    if (geometry != RIAB_GEOM_EUCLIDEAN) return RIAB_EUNSUPPORTED;
-    return random_spatial_dispatch<3>(env, io, anchors, M, targets, n, s);
-  }
-  if (geometry != RIAB_GEOM_EUCLIDEAN) {
-    if (env->n_walls > 4 && !env->walls) return RIAB_EINVAL;
-    if (env->n_walls - 4 > RIAB_MAX_WALLS) return RIAB_ETOOBIG;
-    if (geometry == RIAB_GEOM_GEODESIC && env->n_walls > 5) return RIAB_EUNSUPPORTED;
-  }
-  switch (geometry) {
-    case RIAB_GEOM_EUCLIDEAN: return random_spatial_dispatch<0>(env, io, anchors, M, targets, n, s);
-    case RIAB_GEOM_LINE_OF_SIGHT: return random_spatial_dispatch<1>(env, io, anchors, M, targets, n, s);
-    case RIAB_GEOM_GEODESIC: return random_spatial_dispatch<2>(env, io, anchors, M, targets, n, s);
-    default: return RIAB_EINVAL;
-  }
+  const int bad = place_geometry_check(env, geometry);
+  if (bad) return bad;
+  return visit_place_geometry(env, geometry, [&](auto gx) {
+    return random_spatial_dispatch<decltype(gx)::value>(env, io, anchors, M, targets, n, (hipStream_t)stream);
+  });
 }
 
 extern "C" int riab_grid_cells(const RiabRateIO* io, const float* table, int32_t n, int32_t description, float f0,
@@ -955,16 +867,7 @@ extern "C" int riab_grid_cells(const RiabRateIO* io, const float* table, int32_t
   if (!table) return RIAB_EINVAL;
   const int rc = check_io(io, n, true, false);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (description == RIAB_GC_RECTIFIED) {
-    GridCell<RIAB_GC_RECTIFIED> c{table, f0, 1.0f / (1.0f - f0)};
-    return launch_rate(io, n, c, s);
-  }
-  if (description == RIAB_GC_SHIFTED) {
-    GridCell<RIAB_GC_SHIFTED> c{table, f0, 1.0f};
-    return launch_rate(io, n, c, s);
-  }
-  return RIAB_EINVAL;
+  return visit_grid_desc(description, table, f0, [&](const auto& c) { return launch_rate(io, n, c, (hipStream_t)stream); });
 }
 
 extern "C" int riab_head_direction_cells(const RiabRateIO* io, const float* table, int32_t n,
@@ -1000,8 +903,8 @@ extern "C" int riab_spikes(const RiabRateIO* io, int32_t n, riab_stream_t stream
   const int rc = check_io(io, n, false, false);
   if (rc) return rc;
   if (!io->spikes) return RIAB_EINVAL;
-  dim3 grid;
-  const RateArgs a = make_args(io, n, &grid);
+  RateArgs a = make_args(io, n);
+  const dim3 grid = generic_grid(&a);
   if (io->u_in) hipLaunchKernelGGL((spikes_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL((spikes_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();

@@ -436,13 +436,8 @@ static int launch_pop_rows(const RiabEnv* env, const RiabPopulation* pops, int i
   const RiabPopulation& q = pops[i];
   RiabRateIO io = q.io;
   const float* row = hist + (int64_t)t0 * RIAB_HIST_ROWS * B;
-  io.pos_x = row + (int64_t)RIAB_H_POS_X * B;
-  io.pos_y = row + (int64_t)RIAB_H_POS_Y * B;
-  io.hd_x = row + (int64_t)RIAB_H_HD_X * B;
-  io.hd_y = row + (int64_t)RIAB_H_HD_Y * B;
-  io.pos_ld = (int64_t)RIAB_HIST_ROWS * B;
+  riab::hist_rows_io(&io, row, B, (int64_t)RIAB_HIST_ROWS * B);
   io.T = tc;
-  io.B = B;
   io.rates = q.rates_base + (int64_t)t0 * q.n * B;
   io.spikes = q.spikes_base ? q.spikes_base + (int64_t)t0 * q.n * B : nullptr;
   io.u_in = nullptr;

@@ -197,39 +197,18 @@ struct Step1Task {
 #endif
 #define RIAB_S1_WAVES 8  // waves per workgroup: 0-3 advance the 256 agents, 4-7 draw their normals, all of them write rates
 // one cell group of population `q` (functor `Cell`, CPB cells) for the lane's quad of agents: rate_kernel_wide's inner
-// loop.  `cur`: the group's parameters, one per lane (s1_group_params); `store`: the lanes that write their values.
+// loop (RIAB_CELL_GROUP, riab_rate_cells.h).  `cur`: the group's parameters, one per lane (s1_group_params); `store`: the lanes that write their values.
 template <class Cell, int CPB, int SPK, bool NT>
 __device__ __forceinline__ void s1_group(const Cell& cell, const Step1Pops& ps, const Step1Pop& q, const int gl, const float cur,
                                          const v4f rx, const v4f ry, const v4f rhx, const v4f rhy, const int64_t B,
                                          const uint32_t quad, const bool store) {
-  constexpr int NP = Cell::NP;
-  static_assert(NP * CPB <= 64, "a cell group's parameters must fit one wave");
   const typename Cell::Pos P = cell.from_rows(rx, ry, rhx, rhy);
   const int c0 = gl * CPB;
   int64_t off = (int64_t)c0 * B + 4 * (int64_t)quad;
-  RateArgs sa;  // (what spike_store reads)
-  sa.u_in = nullptr;
-  sa.spikes = q.spikes;
-  sa.tag = q.tag;
-  sa.k0 = ps.k0;
-  sa.k1 = ps.k1;
-  sa.dt = ps.dt;
-#pragma unroll
-  for (int j = 0; j < CPB; ++j) {
-    if (c0 + j < q.n) {  // wave-uniform
-      float p[NP];
-#pragma unroll
-      for (int i = 0; i < NP; ++i) p[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cur), j * NP + i));
-      v4f rr = cell.eval(p, P);
-      rr = finish_rate(rr * q.fr_scale + q.fr_min, P);  // [0,1] -> [min_fr, max_fr]
-      if (store) {
-        if (NT) store_stream<RIAB_STORE_WT>(q.rates + off, rr);
-        else *reinterpret_cast<v4f*>(q.rates + off) = rr;
-        if (SPK && q.spikes) spike_store<false, RIAB_STORE_WT>(sa, rr, off, ps.step0, (uint32_t)(c0 + j), ps.quad0 + quad);  // (wave-uniform)
-      }
-      off += B;
-    }
-  }
+  const SpikeCtx k{q.spikes, nullptr, ps.dt, ps.k0, ps.k1, q.tag};
+  // (the spike test is wave-uniform)
+  RIAB_CELL_GROUP(Cell, CPB, cell, cur, P, c0, q.n, q.fr_scale, q.fr_min, q.rates, off, B, store, NT ? RIAB_STORE_WT : RIAB_STORE_PLAIN,
+                  SPK && q.spikes, false, RIAB_STORE_WT, k, ps.step0, ps.quad0 + quad)
 }
 // ... for a FEW of the segment's quads only (a task's reset has moved an agent or two of the segment: the quads `mq`, a
 // wave-uniform mask): the other way round — a lane takes ONE cell of the group and one of those quads, 64 / CPB quads to
@@ -253,13 +232,7 @@ __device__ __forceinline__ void s1_group_few(const Cell& cell, const Step1Pops& 
   for (int i = 0; i < NP; ++i)
     p[i] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (j * NP + i), __builtin_bit_cast(int, cur)));
   const int c = gl * CPB + j;
-  RateArgs sa;
-  sa.u_in = nullptr;
-  sa.spikes = q.spikes;
-  sa.tag = q.tag;
-  sa.k0 = ps.k0;
-  sa.k1 = ps.k1;
-  sa.dt = ps.dt;
+  const SpikeCtx k{q.spikes, nullptr, ps.dt, ps.k0, ps.k1, q.tag};
   while (mq) {  // (wave-uniform) a round of up to QPR quads
     int my_quad = -1;
     for (int t = 0; t < QPR && mq; ++t) {
@@ -280,9 +253,8 @@ __device__ __forceinline__ void s1_group_few(const Cell& cell, const Step1Pops& 
     if (my_quad >= 0 && c < q.n) {
       const uint32_t quad = quad0 + (uint32_t)my_quad;
       const int64_t off = (int64_t)c * B + 4 * (int64_t)quad;
-      if (NT) store_stream<RIAB_STORE_WT>(q.rates + off, rr);
-      else *reinterpret_cast<v4f*>(q.rates + off) = rr;
-      if (SPK && q.spikes) spike_store<false, RIAB_STORE_WT>(sa, rr, off, ps.step0, (uint32_t)c, ps.quad0 + quad);
+      store_stream<NT ? RIAB_STORE_WT : RIAB_STORE_PLAIN>(q.rates + off, rr);
+      if (SPK && q.spikes) spike_store<false, RIAB_STORE_WT>(k, rr, off, ps.step0, (uint32_t)c, ps.quad0 + quad);
     }
   }
 }
@@ -302,9 +274,7 @@ __device__ __forceinline__ void s1_group_any(const Step1Pops& ps, const Step1Pop
 #define RIAB_S1_PC(DESC, GX, ID)                                                                                        \
   case ID: {                                                                                                            \
     typedef PlaceCell<DESC, GX> CellT;                                                                                  \
-    CellT c;                                                                                                            \
-    c.tab = q.tab; c.scale = q.p0; c.half_scale = q.p1; c.top_hat_w2 = q.p2;                                            \
-    c.walls = nullptr; c.n_internal = 0; c.lds = nullptr;                                                               \
+    const CellT c = place_cell<DESC, GX>(q.tab, q.p0, q.p1, q.p2);                                                      \
     RIAB_S1_RUN(CellT, c, rhx, rhy)                                                                                     \
     break;                                                                                                              \
   }
