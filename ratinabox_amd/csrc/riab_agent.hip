@@ -3,6 +3,7 @@
 #include "riab_agent_kernel.h"
 #include "riab_traj4_kernel.h"
 #include "riab_task_kernel.h"  // (after the motion kernel: this header turns fp contraction off for its own code)
+#include "riab_launch.h"
 
 namespace riab {
 
@@ -20,29 +21,19 @@ __global__ __launch_bounds__(64) void motion_task_kernel(const AgentArgs ma, con
   task_body<MODE>(a, r, pos_x, pos_y, t_env, reward_out, terminal_out, nullptr, gv_scale, gv_x, gv_y, diag);
 }
 
-int launch_motion_task(const AgentArgs& ma, const RiabEnv* env, const RiabTask* task, double* task_state, double* pos_x,
-                       double* pos_y, int64_t task_B, double t_env, double* reward_out, uint8_t* terminal_out,
-                       int32_t* diag, bool auto_reset, int64_t agent_id0, int32_t n_select, int32_t ordered, uint64_t seed,
-                       uint64_t counter, int32_t teleport, float* hist_x, float* hist_y, double* ep_log,
-                       int64_t ep_log_cap, int32_t* ep_count, double gv_scale, double* gv_x, double* gv_y, hipStream_t s) {
+int launch_motion_task(const AgentArgs& ma, const TaskRun& t, hipStream_t s) {
   TaskArgs a;
-  int rc = fill_args(a, env, task, task_state, task_B);
+  ResetArgs r;
+  int mode;
+  const int rc = fill_task_run(a, r, &mode, t);
   if (rc) return rc;
-  if (!pos_x || !pos_y || !reward_out || !terminal_out || !diag) return RIAB_EINVAL;
-  ResetArgs r = {};
-  if (auto_reset) {
-    rc = fill_reset(r, env, agent_id0, n_select, ordered, seed, counter, teleport, nullptr, nullptr, pos_x, pos_y, hist_x,
-                    hist_y, ep_log, ep_log_cap, ep_count);
-    if (rc) return rc;
-  }
   const dim3 grid((unsigned)((ma.B + 63) / 64)), block(64);  // the motion batch is the (padded) larger one
-  const bool gv = gv_x != nullptr;
-#define RIAB_MT_LAUNCH(MODE)                                                                                 \
-  hipLaunchKernelGGL(motion_task_kernel<MODE>, grid, block, 0, s, ma, a, r, pos_x, pos_y, t_env, reward_out, \
-                     terminal_out, gv_scale, gv_x, gv_y, diag)
-  if (auto_reset && gv) RIAB_MT_LAUNCH(7);
-  else if (auto_reset) RIAB_MT_LAUNCH(3);
-  else if (gv) RIAB_MT_LAUNCH(5);
+#define RIAB_MT_LAUNCH(MODE)                                                                                        \
+  hipLaunchKernelGGL(motion_task_kernel<MODE>, grid, block, 0, s, ma, a, r, t.pos_x, t.pos_y, t.t_env, t.reward_out, \
+                     t.terminal_out, t.gv_scale, t.gv_x, t.gv_y, t.diag)
+  if (mode == 7) RIAB_MT_LAUNCH(7);
+  else if (mode == 3) RIAB_MT_LAUNCH(3);
+  else if (mode == 5) RIAB_MT_LAUNCH(5);
   else RIAB_MT_LAUNCH(1);
 #undef RIAB_MT_LAUNCH
   return (int)hipGetLastError();
@@ -85,8 +76,6 @@ int traj_kernel_regs() {
 
 // the forced-position trajectory (Agent.import_trajectory / forced_next_position) of riab_simulate: the single-wave
 // kernel in forced mode, plain stores (what follows it on the stream is ordered by the stream)
-int launch_agent_plain(const AgentArgs& a, hipStream_t s);
-
 int launch_agent_forced(const AgentArgs& a, hipStream_t s) {
   if (!a.forced || !a.hist) return RIAB_EINVAL;
   const dim3 grid((unsigned)((a.B + 63) / 64));

@@ -19,6 +19,7 @@
 #include <type_traits>
 #include "riab_device.h"
 #include "riab_handover.h"
+#include "riab_launch.h"
 
 #ifndef RIAB_BVC_XCH_KB
 #define RIAB_BVC_XCH_KB 1  // pairs of rays per pass over the walls in a workgroup that exchanges its rays (see cast_rays)
@@ -471,11 +472,6 @@ __global__ __launch_bounds__(512) void bvc_kernel(const BvcArgs a) {
     }
   }
 }
-
-int launch_bvc(const RiabEnv* env, const RiabRateIO* io, const double* test_dirs, const double* ray_rden, int32_t K,
-               const float* cells, const float* vm_table, const float* inv_norm, int32_t n, int32_t egocentric,
-               float* ray_out, const int32_t* cell_rows, const int32_t* windows, float* xch, uint32_t* xch_count,
-               uint32_t* xch_arrivals, int n_cus, hipStream_t stream);
 
 }  // namespace riab
 

@@ -17,6 +17,7 @@
 // for, more need the kernel's dynamic-LDS limit raised, and what one workgroup can be given at all (160 KiB on
 // gfx950: 213 objects) bounds the object count (`ovc_object_limit`; more are refused with RIAB_ETOOBIG).
 #include "riab_device.h"
+#include "riab_launch.h"
 
 namespace riab {
 

@@ -12,41 +12,7 @@
 #include <vector>
 
 #include "riab_agent_kernel.h"
-
-namespace riab {
-int launch_task_fused(const RiabEnv* env, const RiabTask* task, double* task_state, double* pos_x, double* pos_y, int64_t B,
-                      double t_env, double* reward_out, uint8_t* terminal_out, int32_t* diag, bool auto_reset,
-                      int64_t agent_id0, int32_t n_select, int32_t ordered, uint64_t seed, uint64_t counter,
-                      int32_t teleport, float* hist_x, float* hist_y, double* ep_log, int64_t ep_log_cap,
-                      int32_t* ep_count, double gv_scale, double* gv_x, double* gv_y, hipStream_t s);
-
-int launch_motion_task(const AgentArgs& ma, const RiabEnv* env, const RiabTask* task, double* task_state, double* pos_x,
-                       double* pos_y, int64_t task_B, double t_env, double* reward_out, uint8_t* terminal_out,
-                       int32_t* diag, bool auto_reset, int64_t agent_id0, int32_t n_select, int32_t ordered, uint64_t seed,
-                       uint64_t counter, int32_t teleport, float* hist_x, float* hist_y, double* ep_log,
-                       int64_t ep_log_cap, int32_t* ep_count, double gv_scale, double* gv_x, double* gv_y, hipStream_t s);
-
-int launch_motion_world(const AgentArgs& ma, const RiabEnv* env, const RiabTask* task, double* task_state, double* world,
-                        const double* pos_x, const double* pos_y, int64_t task_B, double t_env, double* reward_out,
-                        uint8_t* terminal_out, uint64_t* met, int32_t* cand, int32_t* ctl, int32_t* diag, hipStream_t s);
-
-// boundary vector cells with the ray exchange of one-row launches (riab_bvc.hip)
-int launch_bvc(const RiabEnv* env, const RiabRateIO* io, const double* test_dirs, const double* ray_rden, int32_t K,
-               const float* cells, const float* vm_table, const float* inv_norm, int32_t n, int32_t egocentric,
-               float* ray_out, const int32_t* cell_rows, const int32_t* windows, float* xch, uint32_t* xch_count,
-               uint32_t* xch_arrivals, int n_cus, hipStream_t stream);
-
-// the one-launch step (riab_step1.hip)
-int step1_supported(const RiabEnv* env, const RiabPopulation* pop, int64_t B);
-int launch_step1(const AgentArgs& a, const RiabEnv* env, const Step1PopRef* refs, int n_pops, uint64_t seed, uint64_t step_after,
-                 uint32_t* sync_words, uint32_t epoch, bool* walls_ready, int n_cus, hipStream_t s, bool query);
-int launch_step1_task(const AgentArgs& a, const RiabEnv* env, const Step1PopRef* refs, int n_pops, uint64_t seed,
-                      uint64_t step_after, uint32_t* sync_words, uint32_t epoch, bool* walls_ready, int n_cus, const RiabTask* task,
-                      double* task_state, int64_t task_B, double t_env, double* reward_out, uint8_t* terminal_out, int32_t* diag,
-                      bool auto_reset, int32_t n_select, int32_t ordered, uint64_t task_seed, uint64_t counter, int32_t teleport,
-                      double* ep_log, int64_t ep_log_cap, int32_t* ep_count, double gv_scale, double* gv_x, double* gv_y,
-                      double* world, uint64_t* world_met, int32_t* world_cand, int32_t* world_ctl, hipStream_t s, bool query);
-}  // namespace riab
+#include "riab_launch.h"
 
 struct RiabPlan {
   RiabEnv env;
@@ -70,26 +36,11 @@ struct RiabPlan {
   int32_t* diag;
   std::vector<RiabPopulation> pops;
   std::vector<int64_t> pop_fill;
-  // attached task (riab_plan_set_task)
+  // attached task (riab_plan_set_task) whose lanes may be the agents of one world (riab_plan_set_task_world): the record
+  // its launchers take.  tk.t_env and tk.counter are cursors like `step`; hist_x/y and gv_x/y are set per step (task_run)
   bool has_task;
-  RiabTask task;
-  double* task_state;
-  int64_t task_B;
-  double t_env, dt_env;
-  double* reward_out;
-  uint8_t* terminal_out;
-  int32_t* task_diag;
-  int32_t auto_reset, n_select, ordered, teleport;
-  uint64_t task_seed, reset_counter;
-  double* ep_log;
-  int64_t ep_log_cap;
-  int32_t* ep_count;
-  double scripted_speed;
-  // ... whose lanes are the agents of one world (riab_plan_set_task_world); null: every lane its own replica
-  double* world;
-  uint64_t* world_met;
-  int32_t* world_cand;
-  int32_t* world_ctl;
+  riab::TaskRun tk;
+  double dt_env;
   bool action_ready;  // the drift buffer holds the scripted action of the coming step
   // the one-launch step (riab_plan_set_fused)
   uint32_t* sync_words;
@@ -115,6 +66,33 @@ static double plan_clock(RiabPlan* p) {
   return p->clock;
 }
 
+// the tag of the next one-launch step on sync_words (never 0: that is a zeroed word); a query launches nothing and takes none
+static uint32_t next_epoch(RiabPlan* p, bool query) {
+  if (query) return 1u;
+  p->epoch += 1u;
+  if (p->epoch == 0u) p->epoch = 1u;
+  return p->epoch;
+}
+
+// the compute units the plan's launches count on when nobody said (riab_plan_set_compute_units): the device's own count
+static void default_compute_units(RiabPlan* p) {
+  if (p->n_cus > 0) return;
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 1;
+  p->n_cus = n;
+}
+
+// the plan's task record with the values of the step that writes `row` (null: the launch patches the row it stores itself)
+static const riab::TaskRun& task_run(RiabPlan* p, float* row) {
+  riab::TaskRun& t = p->tk;
+  double* const act = t.gv_scale > 0.0 ? const_cast<double*>(p->drift) : nullptr;
+  t.gv_x = act;
+  t.gv_y = act ? act + p->B : nullptr;
+  t.hist_x = row ? row + (int64_t)RIAB_H_POS_X * p->B : nullptr;
+  t.hist_y = row ? row + (int64_t)RIAB_H_POS_Y * p->B : nullptr;
+  return t;
+}
+
 // this step's rows of the plan's fused populations (split: those whose chunk has a free row); returns how many
 static int fused_refs(const RiabPlan* p, riab::Step1PopRef* refs, uint32_t* mask, bool need_free_row) {
   int n = 0;
@@ -136,30 +114,21 @@ static int fused_refs(const RiabPlan* p, riab::Step1PopRef* refs, uint32_t* mask
 
 // One closed-loop step of a plan with a task as ONE kernel: Agent.update(), the rest of TaskEnvironment.step (+ the caller's
 // `if terminal: reset()`, + the next scripted action) and the fused populations' update().  The caller has advanced the
-// plan's step counter and clock.  `query`: nothing is launched; RIAB_OK when there is a kernel for this plan's step.
+// plan's cursors: this reads p->step - 1.  `query`: nothing is launched; RIAB_OK when there is a kernel for this plan's step.
 static int fused_task_step(RiabPlan* p, float* row, hipStream_t s, bool query) {
   riab::AgentArgs ma;
   const uint64_t step_before = query ? p->step : p->step - 1;
   int rc = riab::fill_agent_args(ma, &p->env, &p->motion, p->state, p->B, p->agent_id0, p->drift, nullptr, nullptr, nullptr, p->seed,
                                  step_before, 1, row, p->diag);
   if (rc) return rc;
-  const bool scripted = p->scripted_speed > 0.0;
-  double* act = const_cast<double*>(p->drift);
-  if (scripted && (!act || !p->motion.has_drift)) return RIAB_EINVAL;
+  const riab::TaskRun& t = task_run(p, nullptr);
+  if (t.gv_scale > 0.0 && (!t.gv_x || !p->motion.has_drift)) return RIAB_EINVAL;
   riab::Step1PopRef refs[RIAB_STEP1_MAX_POPS];
   uint32_t mask;
   const int n = fused_refs(p, refs, &mask, false);
-  uint32_t epoch = 1u;
-  if (!query) {
-    p->epoch += 1u;
-    if (p->epoch == 0u) p->epoch = 1u;
-    epoch = p->epoch;
-  }
-  rc = riab::launch_step1_task(ma, &p->env, refs, n, p->seed, step_before + 1, p->sync_words, epoch, &p->walls_ready, p->n_cus,
-                               &p->task, p->task_state, p->task_B, p->t_env, p->reward_out, p->terminal_out, p->task_diag,
-                               p->auto_reset != 0, p->n_select, p->ordered, p->task_seed, p->reset_counter, p->teleport, p->ep_log,
-                               p->ep_log_cap, p->ep_count, p->scripted_speed, scripted ? act : nullptr,
-                               scripted ? act + p->B : nullptr, p->world, p->world_met, p->world_cand, p->world_ctl, s, query);
+  const uint32_t epoch = next_epoch(p, query);
+  rc = riab::launch_step1_task(ma, &p->env, refs, n, p->seed, step_before + 1, p->sync_words, epoch, &p->walls_ready, p->n_cus, t,
+                               s, query);
   if (rc == RIAB_OK && !query) {
     p->fused_steps += 1;
     p->launches += 1;
@@ -180,11 +149,7 @@ static int plan_fused(RiabPlan* p, bool whole_step = false) {
     p->fused_whole = whole_step;
     p->pre_misses.resize(p->pops.size(), 0);
     p->pre_pending.resize(p->pops.size(), 0);
-    if (p->n_cus <= 0) {  // (nobody said: the device's own count)
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 1;
-      p->n_cus = n;
-    }
+    default_compute_units(p);
     int cand[RIAB_STEP1_MAX_POPS];
     int64_t bytes[RIAB_STEP1_MAX_POPS];
     int n = 0;
@@ -236,12 +201,7 @@ static int fused_agent_step(RiabPlan* p, float* row, hipStream_t s, bool need_fr
   int rc = riab::fill_agent_args(ma, &p->env, &p->motion, p->state, p->B, p->agent_id0, p->drift, nullptr, nullptr, nullptr,
                                  p->seed, p->step, 1, row, p->diag);
   if (rc) return rc;
-  uint32_t epoch = 1u;
-  if (!query) {
-    p->epoch += 1u;
-    if (p->epoch == 0u) p->epoch = 1u;
-    epoch = p->epoch;
-  }
+  const uint32_t epoch = next_epoch(p, query);
   rc = riab::launch_step1(ma, &p->env, refs, n, p->seed, p->step + 1, p->sync_words, epoch, &p->walls_ready, p->n_cus, s, query);
   if (rc == RIAB_OK && !query) {
     p->fused_steps += 1;
@@ -273,7 +233,7 @@ extern "C" RiabPlan* riab_plan_create(const RiabEnv* env, const RiabMotion* moti
   p->row_scratch = row_scratch;
   p->diag = diag;
   p->has_task = false;
-  p->world = nullptr;
+  p->tk = riab::TaskRun();
   p->action_ready = false;
   p->sync_words = nullptr;
   p->epoch = 0u;
@@ -353,21 +313,32 @@ extern "C" int riab_plan_set_agent_history(RiabPlan* p, float* hist_base, int64_
   return RIAB_OK;
 }
 
-namespace riab {
-int ovc_object_limit();  // riab_ovc.hip: the most objects the vector-cell kernel's LDS staging holds (-1: no device)
+// What a population must satisfy wherever it is launched from (a step plan, riab_simulate): no more objects than the
+// vector-cell kernel stages, and every input of a feed-forward layer among the `n_before` populations ahead of it.
+int riab::check_population(const RiabPopulation& q, int n_before) {
+  if (q.kind == RIAB_POP_OVC) {
+    const int limit = ovc_object_limit();
+    if (limit >= 0 && q.n_objects > limit) return RIAB_ETOOBIG;
+  }
+  if (q.kind == RIAB_POP_FF) {
+    if (q.n_inputs <= 0 || q.n_inputs > RIAB_FF_MAX_INPUTS) return RIAB_EINVAL;
+    for (int l = 0; l < q.n_inputs; ++l)
+      if (q.input_index[l] < 0 || q.input_index[l] >= n_before) return RIAB_EINVAL;
+  }
+  return RIAB_OK;
 }
 
 extern "C" int riab_plan_add(RiabPlan* p, const RiabPopulation* pop) {
   if (!p || !pop || pop->n <= 0 || pop->kind < RIAB_POP_PLACE || pop->kind > RIAB_POP_THETA_PLACE) return RIAB_EINVAL;
-  if (pop->kind == RIAB_POP_OVC) {  // (a plan that could not take its first step is refused when it is recorded)
-    const int limit = riab::ovc_object_limit();
-    if (limit >= 0 && pop->n_objects > limit) return RIAB_ETOOBIG;
-  }
+  // (a plan that could not take its first step is refused when it is recorded; feed-forward only: an input must already
+  // be in the plan)
+  const int rc = riab::check_population(*pop, (int)p->pops.size());
+  if (rc) return rc;
   if (pop->kind == RIAB_POP_THETA_PLACE && (!pop->table || !(pop->theta_freq > 0.0) || !(pop->kappa >= 0.0))) return RIAB_EINVAL;
   if (pop->kind == RIAB_POP_FF) {
-    if (pop->n_inputs <= 0 || pop->n_inputs > RIAB_FF_MAX_INPUTS || !pop->bias) return RIAB_EINVAL;
-    for (int l = 0; l < pop->n_inputs; ++l)  // feed-forward only: an input must already be in the plan
-      if (pop->input_index[l] < 0 || pop->input_index[l] >= (int)p->pops.size() || !pop->input_wt[l]) return RIAB_EINVAL;
+    if (!pop->bias) return RIAB_EINVAL;
+    for (int l = 0; l < pop->n_inputs; ++l)
+      if (!pop->input_wt[l]) return RIAB_EINVAL;
   }
   p->pops.push_back(*pop);
   p->pop_fill.push_back(0);
@@ -407,7 +378,7 @@ extern "C" int riab_plan_set_task(RiabPlan* p, const RiabTask* task, double* tas
   if (!p) return RIAB_EINVAL;
   p->fused_n = -2;
   p->pre_pending.assign(p->pops.size(), 0);
-  p->world = nullptr;
+  p->tk.world = nullptr;
   if (!task) {
     p->has_task = false;
     return RIAB_OK;
@@ -416,24 +387,30 @@ extern "C" int riab_plan_set_task(RiabPlan* p, const RiabTask* task, double* tas
   if (n_select < 0 || n_select > RIAB_TASK_MAX_GOALS - 1) return RIAB_ETOOBIG;
   if (ep_log && (!ep_count || ep_log_cap <= 0)) return RIAB_EINVAL;
   p->has_task = true;
-  p->task = *task;
-  p->task_state = task_state;
-  p->task_B = task_B;
-  p->t_env = t_env;
+  riab::TaskRun& t = p->tk;
+  t = riab::TaskRun();
+  t.env = &p->env;
+  t.task = *task;
+  t.task_state = task_state;
+  t.task_B = task_B;
+  t.pos_x = p->state + (int64_t)RIAB_S_POS_X * p->B;
+  t.pos_y = p->state + (int64_t)RIAB_S_POS_Y * p->B;
+  t.reward_out = reward_out;
+  t.terminal_out = terminal_out;
+  t.diag = task_diag;
+  t.auto_reset = auto_reset;
+  t.n_select = n_select;
+  t.ordered = ordered;
+  t.teleport = teleport;
+  t.agent_id0 = p->agent_id0;
+  t.seed = task_seed;
+  t.ep_log = ep_log;
+  t.ep_log_cap = ep_log_cap;
+  t.ep_count = ep_count;
+  t.gv_scale = scripted_speed;
+  t.t_env = t_env;
+  t.counter = reset_counter;
   p->dt_env = dt_env;
-  p->reward_out = reward_out;
-  p->terminal_out = terminal_out;
-  p->task_diag = task_diag;
-  p->auto_reset = auto_reset;
-  p->n_select = n_select;
-  p->ordered = ordered;
-  p->task_seed = task_seed;
-  p->reset_counter = reset_counter;
-  p->teleport = teleport;
-  p->ep_log = ep_log;
-  p->ep_log_cap = ep_log_cap;
-  p->ep_count = ep_count;
-  p->scripted_speed = scripted_speed;
   p->action_ready = false;
   return RIAB_OK;
 }
@@ -441,15 +418,15 @@ extern "C" int riab_plan_set_task(RiabPlan* p, const RiabTask* task, double* tas
 extern "C" int riab_plan_set_task_world(RiabPlan* p, double* world, uint64_t* met_scratch, int32_t* cand_scratch, int32_t* ctl) {
   if (!p || !p->has_task) return RIAB_EINVAL;
   if (world && (!met_scratch || !cand_scratch || !ctl)) return RIAB_EINVAL;
-  p->world = world;
-  p->world_met = met_scratch;
-  p->world_cand = cand_scratch;
-  p->world_ctl = ctl;
+  p->tk.world = world;
+  p->tk.world_met = met_scratch;
+  p->tk.world_cand = cand_scratch;
+  p->tk.world_ctl = ctl;
   p->fused_n = -2;
   return RIAB_OK;
 }
 
-extern "C" double riab_plan_task_clock(const RiabPlan* p) { return p && p->has_task ? p->t_env : 0.0; }
+extern "C" double riab_plan_task_clock(const RiabPlan* p) { return p && p->has_task ? p->tk.t_env : 0.0; }
 
 extern "C" int riab_plan_set_clock(RiabPlan* p, double t) {
   if (!p || !(t == t)) return RIAB_EINVAL;
@@ -473,90 +450,90 @@ extern "C" int64_t riab_plan_rows_free(const RiabPlan* p) {
 
 extern "C" uint64_t riab_plan_step_index(const RiabPlan* p) { return p ? p->step : 0; }
 
-static int launch_population(RiabPlan* p, size_t i, const float* row, hipStream_t s) {
-  RiabPopulation& q = p->pops[i];
-  const int64_t B = p->B;
+// Neurons.update() of one population on T successive history rows: the population's kernel, then — for a population with
+// additive OU noise — the noise pass and the spikes drawn on the final rates.  The one launcher of a step plan's one-row
+// launches and of riab_simulate's chunks; where the two differ, the record says so:
+//   io.step0      plan: its step cursor, already advanced | simulate: step0 + 1 + t0
+//   BVC           plan: the ray exchange (r.xch_arrivals, r.n_cus resolved by the caller) | simulate: no exchange (null, 0)
+//   FeedForward   plan: T = 1, input j read at r.cursors[j] - 1 (row 0 without history), rates_prime written |
+//                 simulate: T = tc, inputs read at rate_row = t0, rates_prime not written
+//   velocity and phase-precessing cells read r.state and r.clock: a plan's; riab_simulate refuses them with
+//                 RIAB_EUNSUPPORTED before anything is launched (check_populations)
+//   `launches`    plan: += 1, + 1 for a layer's spike pass, + 1 or 2 for noise (with spikes) | simulate: null
+int riab::launch_population_rows(const PopRows& r, hipStream_t s, int64_t* launches) {
+  const RiabEnv* env = r.env;
+  const RiabPopulation& q = r.pops[r.index];
+  const int64_t B = r.B;
   RiabRateIO io = q.io;
-  riab::hist_rows_io(&io, row, B, B);
-  io.T = 1;
-  const int64_t r = p->pop_fill[i];
-  io.rates = q.rates_base + r * (int64_t)q.n * B;
-  io.spikes = q.spikes_base ? q.spikes_base + r * (int64_t)q.n * B : nullptr;
+  hist_rows_io(&io, r.hist, B, r.hist_ld);
+  io.T = r.T;
+  io.rates = q.rates_base + r.rate_row * q.n * B;
+  io.spikes = q.spikes_base ? q.spikes_base + r.rate_row * q.n * B : nullptr;
   io.u_in = nullptr;
-  io.dt = (float)p->motion.dt;
-  io.seed = p->seed;
-  io.step0 = p->step;  // Neurons.update after the p->step-th Agent.update (the cursor was already advanced)
-  io.agent_id0 = p->agent_id0;
+  io.dt = r.dt;
+  io.seed = r.seed;
+  io.step0 = r.step0;
+  io.agent_id0 = r.agent_id0;
   const bool noisy = q.noise_state != nullptr;
   uint8_t* const spikes = io.spikes;
   if (noisy) io.spikes = nullptr;  // spikes are drawn on the final rate, after the noise has been added
-  int rc = RIAB_EINVAL;
+  // (a kind without a case, a reader of the state without one: RIAB_EUNSUPPORTED, not reachable behind the callers' checks)
+  int rc = RIAB_EUNSUPPORTED;
   switch (q.kind) {
-    case RIAB_POP_PLACE:
-      rc = riab_place_cells(&p->env, &io, q.table, q.n, q.description, q.geometry, q.top_hat_width, s);
-      break;
-    case RIAB_POP_GRID:
-      rc = riab_grid_cells(&io, q.table, q.n, q.description, q.f0, s);
-      break;
-    case RIAB_POP_HDC:
-      rc = riab_head_direction_cells(&io, q.table, q.n, s);
-      break;
+    case RIAB_POP_PLACE: rc = riab_place_cells(env, &io, q.table, q.n, q.description, q.geometry, q.top_hat_width, s); break;
+    case RIAB_POP_GRID: rc = riab_grid_cells(&io, q.table, q.n, q.description, q.f0, s); break;
+    case RIAB_POP_HDC: rc = riab_head_direction_cells(&io, q.table, q.n, s); break;
     case RIAB_POP_VELOCITY:  // Agent.velocity: rows of the float64 state, not of the history record
-      rc = riab_velocity_cells(&io, q.table, q.n, q.one_sigma_speed, p->state + RIAB_S_VEL_X * B,
-                               p->state + RIAB_S_VEL_Y * B, s);
+      if (!r.state) break;
+      rc = riab_velocity_cells(&io, q.table, q.n, q.one_sigma_speed, r.state + RIAB_S_VEL_X * B, r.state + RIAB_S_VEL_Y * B, s);
       break;
-    case RIAB_POP_THETA_PLACE: {  // Agent.velocity and Agent.t: the float64 state rows and the plan's clock
-      const double period = 1.0 / q.theta_freq;
-      rc = riab_phase_precessing_place_cells(&p->env, &io, q.table, q.n, q.description, q.geometry, q.top_hat_width, q.kappa,
-                                             q.theta_freq * fmod(plan_clock(p), period), p->state + RIAB_S_VEL_X * B,
-                                             p->state + RIAB_S_VEL_Y * B, s);
+    case RIAB_POP_THETA_PLACE:  // Agent.velocity and Agent.t: the float64 state rows and the plan's clock
+      if (!r.state) break;
+      rc = riab_phase_precessing_place_cells(env, &io, q.table, q.n, q.description, q.geometry, q.top_hat_width, q.kappa,
+                                             q.theta_freq * fmod(r.clock, 1.0 / q.theta_freq), r.state + RIAB_S_VEL_X * B,
+                                             r.state + RIAB_S_VEL_Y * B, s);
       break;
-    }
-    case RIAB_POP_SPEED:  // history["vel"][-1]: the measured velocity of the step just taken
-      io.hd_x = row + RIAB_H_VEL_X * B;
-      io.hd_y = row + RIAB_H_VEL_Y * B;
+    case RIAB_POP_SPEED:  // history["vel"]: the measured velocity of the steps just taken
+      io.hd_x = r.hist + RIAB_H_VEL_X * B;
+      io.hd_y = r.hist + RIAB_H_VEL_Y * B;
       rc = riab_speed_cell(&io, q.one_sigma_speed, s);
       break;
     case RIAB_POP_RANDOM_SPATIAL:
-      rc = riab_random_spatial_neurons(&p->env, &io, q.table, q.n_anchors, q.targets, q.n, q.geometry, s);
+      rc = riab_random_spatial_neurons(env, &io, q.table, q.n_anchors, q.targets, q.n, q.geometry, s);
       break;
     case RIAB_POP_BVC: {
-      if (p->n_cus <= 0) {  // (nobody said: the device's own count)
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 1;
-        p->n_cus = n;
-      }
-      if (p->xch_arrivals.size() < p->pops.size()) p->xch_arrivals.resize(p->pops.size(), 0u);
-      rc = riab::launch_bvc(&p->env, &io, q.test_dirs, q.ray_rden, q.K, q.table, q.vm_table, q.inv_norm, q.n, q.egocentric,
-                            nullptr, q.cell_rows, q.windows, q.bvc_xch, q.bvc_xch_count, &p->xch_arrivals[i], p->n_cus, s);
+      const bool xch = r.xch_arrivals != nullptr;
+      rc = launch_bvc(env, &io, q.test_dirs, q.ray_rden, q.K, q.table, q.vm_table, q.inv_norm, q.n, q.egocentric, nullptr,
+                      q.cell_rows, q.windows, xch ? q.bvc_xch : nullptr, xch ? q.bvc_xch_count : nullptr, r.xch_arrivals,
+                      xch ? r.n_cus : 0, s);
       break;
     }
     case RIAB_POP_OVC:
-      rc = riab_object_vector_cells(&p->env, &io, q.objects, q.object_types, q.n_objects, q.table, q.n, q.walls_occlude,
+      rc = riab_object_vector_cells(env, &io, q.objects, q.object_types, q.n_objects, q.table, q.n, q.walls_occlude,
                                     q.egocentric, s);
       break;
     case RIAB_POP_FF: {
       RiabFFInput in[RIAB_FF_MAX_INPUTS];
       for (int l = 0; l < q.n_inputs; ++l) {
         const int j = q.input_index[l];
-        const RiabPopulation& src = p->pops[j];
-        // population j < i has been launched this step already: its cursor points past the row it wrote
-        const int64_t row_j = src.capacity_rows > 0 ? p->pop_fill[j] - 1 : 0;
-        in[l].rates = src.rates_base + row_j * (int64_t)src.n * B;
+        const RiabPopulation& src = r.pops[j];  // (an earlier population: its rows of this step / chunk exist)
+        const int64_t row_j = !r.cursors ? r.rate_row : (src.capacity_rows > 0 ? r.cursors[j] - 1 : 0);
+        in[l].rates = src.rates_base + row_j * src.n * B;
         in[l].wt = q.input_wt[l];
         in[l].n_in = src.n;
       }
-      rc = riab_feedforward(in, q.n_inputs, q.bias, q.n, 1, B, q.activation, q.act_params, io.rates, q.rates_prime, s);
+      rc = riab_feedforward(in, q.n_inputs, q.bias, q.n, r.T, B, q.activation, q.act_params, io.rates,
+                            r.write_prime ? q.rates_prime : nullptr, s);
       if (rc == RIAB_OK && io.spikes) rc = riab_spikes(&io, q.n, s);
       break;
     }
   }
   if (rc) return rc;
-  p->launches += (q.kind == RIAB_POP_FF && io.spikes) ? 2 : 1;
+  if (launches) *launches += (q.kind == RIAB_POP_FF && io.spikes) ? 2 : 1;
   if (noisy) {
-    p->launches += spikes ? 2 : 1;
-    rc = riab_neuron_noise(q.noise_state, io.rates, nullptr, q.n, B, 1, q.noise_theta_dt, q.noise_sigma_dt, p->seed, p->step,
-                           q.io.pop_id, p->agent_id0, s);
+    if (launches) *launches += spikes ? 2 : 1;
+    rc = riab_neuron_noise(q.noise_state, io.rates, nullptr, q.n, B, r.T, q.noise_theta_dt, q.noise_sigma_dt, r.seed, r.step0,
+                           q.io.pop_id, r.agent_id0, s);
     if (rc) return rc;
     if (spikes) {
       io.spikes = spikes;
@@ -564,6 +541,55 @@ static int launch_population(RiabPlan* p, size_t i, const float* row, hipStream_
     }
   }
   return rc;
+}
+
+// Neurons.update() of population i on the history row `row`, after the p->step-th Agent.update() (the cursor was advanced)
+static int launch_population(RiabPlan* p, size_t i, const float* row, hipStream_t s) {
+  riab::PopRows r = {};
+  r.env = &p->env;
+  r.pops = p->pops.data();
+  r.index = (int)i;
+  r.hist = row;
+  r.hist_ld = p->B;
+  r.B = p->B;
+  r.T = 1;
+  r.rate_row = p->pop_fill[i];
+  r.dt = (float)p->motion.dt;
+  r.seed = p->seed;
+  r.step0 = p->step;
+  r.agent_id0 = p->agent_id0;
+  r.state = p->state;
+  if (p->pops[i].kind == RIAB_POP_THETA_PLACE) r.clock = plan_clock(p);
+  if (p->pops[i].kind == RIAB_POP_BVC) {
+    default_compute_units(p);
+    if (p->xch_arrivals.size() < p->pops.size()) p->xch_arrivals.resize(p->pops.size(), 0u);
+    r.xch_arrivals = &p->xch_arrivals[i];
+    r.n_cus = p->n_cus;
+  }
+  r.cursors = p->pop_fill.data();  // (population j < i has been launched this step already: its cursor points past the row it wrote)
+  r.write_prime = true;
+  return riab::launch_population_rows(r, s, &p->launches);
+}
+
+// A row written ahead (riab_plan_step_agent) that its population did not claim is a miss of that population; two in a row
+// leave it out of the one-launch step.
+static void count_missed_rows(RiabPlan* p) {
+  for (size_t i = 0; i < p->pre_pending.size(); ++i) {
+    if (!p->pre_pending[i]) continue;
+    p->pre_pending[i] = 0;
+    if (++p->pre_misses[i] == 2) p->fused_n = -2;
+  }
+}
+
+// One step taken: the RNG counter and the agent's history row; `task`: the task's clock too, and the counter of the
+// resets the plan decides on the device.
+static void advance_cursors(RiabPlan* p, bool task) {
+  p->step += 1;
+  if (p->hist_base) p->hist_fill += 1;
+  if (task) {
+    p->tk.t_env += p->dt_env;
+    if (p->tk.auto_reset) p->tk.counter += 1;
+  }
 }
 
 // The two halves of a plan step, for callers that keep the reference's call structure — `Ag.update()` here,
@@ -582,17 +608,12 @@ extern "C" int riab_plan_step_agent(RiabPlan* p, riab_stream_t stream) {
   // populations' own calls, which then only move their cursors (same inputs, same rows, same bits).  A row written ahead
   // that nobody claims (a loop that does not update that population after every agent step) is a miss; two in a row
   // leave the population out.
-  for (size_t i = 0; i < p->pre_pending.size(); ++i) {
-    if (!p->pre_pending[i]) continue;
-    p->pre_pending[i] = 0;
-    if (++p->pre_misses[i] == 2) p->fused_n = -2;
-  }
+  count_missed_rows(p);
   if (plan_fused(p) > 0) {
     uint32_t mask = 0u;
     const int rc = fused_agent_step(p, row, (hipStream_t)stream, true, &mask, false);
     if (rc == RIAB_OK) {
-      p->step += 1;
-      if (p->hist_base) p->hist_fill += 1;
+      advance_cursors(p, false);
       for (int k = 0; k < p->fused_n; ++k)
         if (mask & (1u << k)) p->pre_pending[p->fused[k]] = 1;
       p->pre_step = p->step;
@@ -605,8 +626,7 @@ extern "C" int riab_plan_step_agent(RiabPlan* p, riab_stream_t stream) {
   if (rc) return rc;
   p->launches += 1;
   if (forced) p->forced_fill += 1;
-  p->step += 1;
-  if (p->hist_base) p->hist_fill += 1;
+  advance_cursors(p, false);
   return RIAB_OK;
 }
 
@@ -617,11 +637,7 @@ extern "C" int riab_plan_step_agent(RiabPlan* p, riab_stream_t stream) {
 // one-launch step off for them; one claimed row switches it on again.
 extern "C" int riab_plan_discard_ahead(RiabPlan* p) {
   if (!p) return RIAB_EINVAL;
-  for (size_t i = 0; i < p->pre_pending.size(); ++i) {
-    if (!p->pre_pending[i]) continue;
-    p->pre_pending[i] = 0;
-    if (++p->pre_misses[i] == 2) p->fused_n = -2;
-  }
+  count_missed_rows(p);
   return RIAB_OK;
 }
 
@@ -648,6 +664,108 @@ extern "C" int riab_plan_step_population(RiabPlan* p, int32_t index, riab_stream
   return RIAB_OK;
 }
 
+// The scripted action of the plan's FIRST step (and of every step without auto-reset): later steps get theirs from the
+// previous step's task / reset launch (action_ready).
+static int first_action(RiabPlan* p, hipStream_t s) {
+  const riab::TaskRun& t = p->tk;
+  double* act = const_cast<double*>(p->drift);
+  if (!act || !p->motion.has_drift) return RIAB_EINVAL;
+  if (p->action_ready) return RIAB_OK;
+  const int rc = t.world ? riab_task_world_goal_vector(&p->env, &t.task, t.task_state, t.world, t.pos_x, t.pos_y, t.task_B,
+                                                       t.gv_scale, act, act + p->B, s)
+                         : riab_task_goal_vector(&p->env, &t.task, t.task_state, t.pos_x, t.pos_y, t.task_B, t.gv_scale, act,
+                                                 act + p->B, s);
+  if (rc == RIAB_OK) p->launches += 1;
+  return rc;
+}
+
+// Agent.update() of one step on `row`, with the plan's task when it has one, in one of five forms.  n_fused > 0: one of the
+// two one-launch forms, which carry the fused populations' update() as well.
+// Cursor order: the forms that launch motion and task together advance the cursors BEFORE the launch (fused_task_step
+// reads p->step - 1; the task's kernels take the clock after the step) and leave them advanced when the launch fails;
+// the plain form advances them after riab_agent_step has returned RIAB_OK.
+// action_ready is set by every launch that leaves the coming step's scripted action in the drift buffer and cleared by
+// the one that does not (the world's step, until its reset has been launched).
+static int motion_stage(RiabPlan* p, float* row, hipStream_t s, int n_fused) {
+  int rc;
+  if (!p->has_task && n_fused > 0) {  // Agent.update() and the fused populations' update(): one kernel (riab_step1.hip)
+    uint32_t mask;
+    rc = fused_agent_step(p, row, s, false, &mask, false);
+    if (rc) return rc;
+    advance_cursors(p, false);
+    return RIAB_OK;
+  }
+  const bool scripted = p->has_task && p->tk.gv_scale > 0.0;
+  if (n_fused > 0) {  // ... with the task's (or world's) step, its reset and the next action as well (TASK modes)
+    advance_cursors(p, true);
+    rc = fused_task_step(p, row, s, false);
+    if (rc) return rc;
+    p->action_ready = scripted;
+    return RIAB_OK;
+  }
+  const bool world = p->has_task && p->tk.world;
+  if (world || (p->has_task && riab::g_options[RIAB_OPT_FUSED_TASK] != 0)) {  // (A/B: 0 = motion and task launched separately)
+    riab::AgentArgs ma;
+    rc = riab::fill_agent_args(ma, &p->env, &p->motion, p->state, p->B, p->agent_id0, p->drift, nullptr, nullptr, nullptr,
+                               p->seed, p->step, 1, row, p->diag);
+    if (rc) return rc;
+    const riab::TaskRun& t = task_run(p, row);
+    if (!world) {  // Agent.update() + the rest of TaskEnvironment.step (+ reset, + next action) in one launch
+      advance_cursors(p, true);
+      rc = riab::launch_motion_task(ma, t, s);
+      if (rc) return rc;
+      p->launches += 1;
+      p->action_ready = scripted;
+      return RIAB_OK;
+    }
+    // Agent.update() + the world's step in one launch, the world's reset in a second: ITS counter moves between the two
+    advance_cursors(p, false);
+    p->tk.t_env += p->dt_env;
+    rc = riab::launch_motion_world(ma, t, s);
+    if (rc) return rc;
+    p->launches += 1;
+    p->action_ready = false;
+    if (t.auto_reset) {  // the caller's `if terminal: env.reset()`, decided on the device, and the next scripted action
+      p->tk.counter += 1;
+      rc = riab_task_world_reset(&p->env, &t.task, t.task_state, t.world, t.task_B, t.agent_id0, t.t_env, t.n_select, t.ordered,
+                                 t.seed, t.counter, t.teleport, nullptr, nullptr, t.pos_x, t.pos_y, t.hist_x, t.hist_y, t.ep_log,
+                                 t.ep_log_cap, t.ep_count, 1, t.gv_scale, t.gv_x, t.gv_y, t.diag, s);
+      if (rc) return rc;
+      p->launches += 1;
+      p->action_ready = scripted;
+    }
+    return RIAB_OK;
+  }
+  // Agent.update(), then the task's launch, if any
+  const double* forced = p->forced ? p->forced + p->forced_fill * 2 * p->B : nullptr;
+  rc = riab_agent_step(&p->env, &p->motion, p->state, p->B, p->agent_id0, p->drift, nullptr, nullptr, forced, nullptr, p->seed,
+                       p->step, 1, row, p->diag, s);
+  if (rc) return rc;
+  p->launches += 1;
+  if (forced) p->forced_fill += 1;
+  advance_cursors(p, p->has_task);
+  if (p->has_task) {  // the rest of TaskEnvironment.step (+ the caller's `if terminal: reset()`)
+    rc = riab::launch_task_fused(task_run(p, row), s);
+    if (rc) return rc;
+    p->launches += 1;
+    p->action_ready = scripted;
+  }
+  return RIAB_OK;
+}
+
+// Neurons.update() of every population the motion stage's launch did not carry, in list order, and every population's
+// row cursor: the one place a plan step launches populations.
+static int rest_of_populations(RiabPlan* p, const float* row, hipStream_t s, bool skip_fused) {
+  for (size_t i = 0; i < p->pops.size(); ++i) {
+    if (!skip_fused || !is_fused(p, (int)i)) {
+      const int rc = launch_population(p, i, row, s);
+      if (rc) return rc;
+    }
+    if (p->pops[i].capacity_rows > 0) p->pop_fill[i] += 1;
+  }
+  return RIAB_OK;
+}
+
 extern "C" int riab_plan_step(RiabPlan* p, int32_t n_steps, riab_stream_t stream) {
   if (!p || n_steps <= 0) return RIAB_EINVAL;
   if (riab_plan_rows_free(p) < n_steps) return RIAB_EFULL;
@@ -657,151 +775,10 @@ extern "C" int riab_plan_step(RiabPlan* p, int32_t n_steps, riab_stream_t stream
   const int n_fused = plan_fused(p, true);
   for (int32_t k = 0; k < n_steps; ++k) {
     float* row = p->hist_base ? p->hist_base + p->hist_fill * (int64_t)RIAB_HIST_ROWS * p->B : p->row_scratch;
-    if (n_fused > 0 && !p->has_task) {  // Agent.update() and the fused populations' update() in one launch, the others after it
-      uint32_t mask;
-      int rc = fused_agent_step(p, row, s, false, &mask, false);
-      if (rc) return rc;
-      p->step += 1;
-      if (p->hist_base) p->hist_fill += 1;
-      for (size_t i = 0; i < p->pops.size(); ++i) {
-        if (!is_fused(p, (int)i)) {
-          rc = launch_population(p, i, row, s);
-          if (rc) return rc;
-        }
-        if (p->pops[i].capacity_rows > 0) p->pop_fill[i] += 1;
-      }
-      continue;
-    }
-    double* pos_x = p->state + (int64_t)RIAB_S_POS_X * p->B;
-    double* pos_y = p->state + (int64_t)RIAB_S_POS_Y * p->B;
-    int rc;
-    const bool scripted = p->has_task && p->scripted_speed > 0.0;
-    double* act = const_cast<double*>(p->drift);
-    if (p->has_task && p->world) {  // the lanes are the agents of ONE world
-      if (scripted) {
-        if (!act || !p->motion.has_drift) return RIAB_EINVAL;
-        if (!p->action_ready) {  // first step / no auto-reset: later ones get their action from the previous step's reset launch
-          rc = riab_task_world_goal_vector(&p->env, &p->task, p->task_state, p->world, pos_x, pos_y, p->task_B,
-                                           p->scripted_speed, act, act + p->B, s);
-          if (rc) return rc;
-          p->launches += 1;
-        }
-      }
-      if (n_fused > 0) {  // Agent.update, the world's step, its reset when the episode ended, the next action and the fused
-        p->step += 1;     // populations' update(): ONE kernel (riab_step1.hip, TASK & 8)
-        if (p->hist_base) p->hist_fill += 1;
-        p->t_env += p->dt_env;
-        if (p->auto_reset) p->reset_counter += 1;
-        rc = fused_task_step(p, row, s, false);
-        if (rc) return rc;
-        p->action_ready = scripted;
-        for (size_t i = 0; i < p->pops.size(); ++i) {
-          if (!is_fused(p, (int)i)) {
-            rc = launch_population(p, i, row, s);
-            if (rc) return rc;
-          }
-          if (p->pops[i].capacity_rows > 0) p->pop_fill[i] += 1;
-        }
-        continue;
-      }
-      riab::AgentArgs ma;  // Agent.update and the world's step in one launch
-      rc = riab::fill_agent_args(ma, &p->env, &p->motion, p->state, p->B, p->agent_id0, p->drift, nullptr, nullptr, nullptr,
-                                 p->seed, p->step, 1, row, p->diag);
-      if (rc) return rc;
-      p->step += 1;
-      if (p->hist_base) p->hist_fill += 1;
-      p->t_env += p->dt_env;
-      rc = riab::launch_motion_world(ma, &p->env, &p->task, p->task_state, p->world, pos_x, pos_y, p->task_B, p->t_env,
-                                     p->reward_out, p->terminal_out, p->world_met, p->world_cand, p->world_ctl, p->task_diag, s);
-      if (rc) return rc;
-      p->launches += 1;
-      p->action_ready = false;
-      if (p->auto_reset) {  // the caller's `if terminal: env.reset()`, decided on the device, and the next scripted action
-        p->reset_counter += 1;
-        rc = riab_task_world_reset(&p->env, &p->task, p->task_state, p->world, p->task_B, p->agent_id0, p->t_env, p->n_select,
-                                   p->ordered, p->task_seed, p->reset_counter, p->teleport, nullptr, nullptr, pos_x, pos_y,
-                                   row + (int64_t)RIAB_H_POS_X * p->B, row + (int64_t)RIAB_H_POS_Y * p->B, p->ep_log,
-                                   p->ep_log_cap, p->ep_count, 1, p->scripted_speed, scripted ? act : nullptr,
-                                   scripted ? act + p->B : nullptr, p->task_diag, s);
-        if (rc) return rc;
-        p->launches += 1;
-        p->action_ready = scripted;
-      }
-      for (size_t i = 0; i < p->pops.size(); ++i) {
-        rc = launch_population(p, i, row, s);
-        if (rc) return rc;
-        if (p->pops[i].capacity_rows > 0) p->pop_fill[i] += 1;
-      }
-      continue;
-    }
-    if (scripted) {
-      if (!act || !p->motion.has_drift) return RIAB_EINVAL;
-      if (!p->action_ready) {  // first step: later ones get their action from the previous step's fused task kernel
-        rc = riab_task_goal_vector(&p->env, &p->task, p->task_state, pos_x, pos_y, p->task_B, p->scripted_speed, act,
-                                   act + p->B, s);
-        if (rc) return rc;
-        p->launches += 1;
-      }
-    }
-    const bool fused = p->has_task && riab::g_options[RIAB_OPT_FUSED_TASK] != 0;  // (A/B: 0 = motion and task launched separately)
-    if (fused) {  // motion + the rest of TaskEnvironment.step (+ the caller's `if terminal: reset()`) in one launch
-      riab::AgentArgs ma;
-      rc = riab::fill_agent_args(ma, &p->env, &p->motion, p->state, p->B, p->agent_id0, p->drift, nullptr, nullptr, nullptr,
-                                 p->seed, p->step, 1, row, p->diag);
-      if (rc) return rc;
-      p->step += 1;
-      if (p->hist_base) p->hist_fill += 1;
-      p->t_env += p->dt_env;
-      if (p->auto_reset) p->reset_counter += 1;
-      if (n_fused > 0) {  // ... and the fused populations' update() as well: the whole closed-loop step is one kernel
-        rc = fused_task_step(p, row, s, false);
-        if (rc) return rc;
-        p->action_ready = scripted;
-        for (size_t i = 0; i < p->pops.size(); ++i) {
-          if (!is_fused(p, (int)i)) {
-            rc = launch_population(p, i, row, s);
-            if (rc) return rc;
-          }
-          if (p->pops[i].capacity_rows > 0) p->pop_fill[i] += 1;
-        }
-        continue;
-      }
-      rc = riab::launch_motion_task(ma, &p->env, &p->task, p->task_state, pos_x, pos_y, p->task_B, p->t_env, p->reward_out,
-                                    p->terminal_out, p->task_diag, p->auto_reset != 0, p->agent_id0, p->n_select,
-                                    p->ordered, p->task_seed, p->reset_counter, p->teleport,
-                                    row + (int64_t)RIAB_H_POS_X * p->B, row + (int64_t)RIAB_H_POS_Y * p->B, p->ep_log,
-                                    p->ep_log_cap, p->ep_count, p->scripted_speed, scripted ? act : nullptr,
-                                    scripted ? act + p->B : nullptr, s);
-      if (rc) return rc;
-      p->launches += 1;
-      p->action_ready = scripted;
-    } else {
-    const double* forced = p->forced ? p->forced + p->forced_fill * 2 * p->B : nullptr;
-    rc = riab_agent_step(&p->env, &p->motion, p->state, p->B, p->agent_id0, p->drift, nullptr, nullptr, forced, nullptr,
-                         p->seed, p->step, 1, row, p->diag, s);
+    int rc = p->has_task && p->tk.gv_scale > 0.0 ? first_action(p, s) : RIAB_OK;
+    if (!rc) rc = motion_stage(p, row, s, n_fused);
+    if (!rc) rc = rest_of_populations(p, row, s, n_fused > 0);
     if (rc) return rc;
-    p->launches += 1;
-    if (forced) p->forced_fill += 1;
-    p->step += 1;
-    if (p->hist_base) p->hist_fill += 1;
-    if (p->has_task) {  // the rest of TaskEnvironment.step (+ the caller's `if terminal: reset()`)
-      p->t_env += p->dt_env;
-      if (p->auto_reset) p->reset_counter += 1;
-      rc = riab::launch_task_fused(&p->env, &p->task, p->task_state, pos_x, pos_y, p->task_B, p->t_env, p->reward_out,
-                                   p->terminal_out, p->task_diag, p->auto_reset != 0, p->agent_id0, p->n_select, p->ordered,
-                                   p->task_seed, p->reset_counter, p->teleport, row + (int64_t)RIAB_H_POS_X * p->B,
-                                   row + (int64_t)RIAB_H_POS_Y * p->B, p->ep_log, p->ep_log_cap, p->ep_count,
-                                   p->scripted_speed, scripted ? act : nullptr, scripted ? act + p->B : nullptr, s);
-      if (rc) return rc;
-      p->launches += 1;
-      p->action_ready = scripted;
-    }
-    }
-    for (size_t i = 0; i < p->pops.size(); ++i) {
-      rc = launch_population(p, i, row, s);
-      if (rc) return rc;
-      if (p->pops[i].capacity_rows > 0) p->pop_fill[i] += 1;
-    }
   }
   return RIAB_OK;
 }

@@ -24,6 +24,7 @@
 #include "riab_device.h"
 #include "riab_rate_cells.h"
 #include "riab_handover.h"
+#include "riab_launch.h"
 // how the spike bytes of the open-loop kernels are stored (riab_device.h: store_stream)
 #ifndef RIAB_SPIKE_POLICY_GATED
 #define RIAB_SPIKE_POLICY_GATED RIAB_STORE_NT
@@ -614,7 +615,6 @@ static uint32_t serial_gap_ticks() {
   return ticks;
 }
 
-int traj_kernel_regs();   // riab_agent.hip
 // one rate_kernel_gated launch, as launch_rate_stream describes it to launch_stream_cell
 struct StreamLaunch {
   StreamArgs st;

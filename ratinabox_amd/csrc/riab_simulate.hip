@@ -42,20 +42,7 @@
 #include <vector>
 
 #include "riab_agent_kernel.h"
-
-namespace riab {
-int launch_agent_pub(const AgentArgs& a, hipStream_t s, bool* state_published);
-int launch_agent_forced(const AgentArgs& a, hipStream_t s);
-int launch_agent_plain(const AgentArgs& a, hipStream_t s);
-int stream_supported(const RiabEnv* env, const RiabPopulation* pop, int64_t B);
-int launch_rate_stream(const RiabEnv* env, const RiabPopulation* pop, const float* hist, int64_t B, int32_t T, float dt,
-                       uint64_t seed, uint64_t step0, int64_t agent_id0, uint32_t* ctrl, uint32_t spin_limit, bool stamps,
-                       hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, bool dry_run, bool reserve,
-                       uint32_t serial_rows);
-int launch_stream_gate(uint32_t* ctrl, uint32_t started_target, uint32_t n_traj, uint32_t progress_target,
-                       uint32_t spin_limit, bool sleep_long, uint32_t final_target, hipStream_t s);
-int launch_stream_open(uint32_t* ctrl, uint32_t n_traj, uint32_t step_base, hipStream_t s);
-}  // namespace riab
+#include "riab_launch.h"
 
 struct RiabStreamer {
   hipStream_t side;          // the trajectory kernel's stream (SIDE_STREAM 0): BORROWED from the process-wide pool of screened
@@ -429,98 +416,37 @@ extern "C" float riab_streamer_last_rate_ms(RiabStreamer* h) {
 
 
 // ---- any set of populations: the chunked form of the rate stage for all of them, one native call ----------------
-// rows [t0, t0 + tc) of population i from the trajectory rows of the same chunk (the T-row form of riab_plan.hip's
-// launch_population: same entry points, same arguments as `tc` calls of Neurons.update on successive rows)
-static int launch_pop_rows(const RiabEnv* env, const RiabPopulation* pops, int i, const float* hist, int64_t B, int32_t t0,
-                           int32_t tc, float dt, uint64_t seed, uint64_t step0, int64_t agent_id0, hipStream_t s) {
-  const RiabPopulation& q = pops[i];
-  RiabRateIO io = q.io;
-  const float* row = hist + (int64_t)t0 * RIAB_HIST_ROWS * B;
-  riab::hist_rows_io(&io, row, B, (int64_t)RIAB_HIST_ROWS * B);
-  io.T = tc;
-  io.rates = q.rates_base + (int64_t)t0 * q.n * B;
-  io.spikes = q.spikes_base ? q.spikes_base + (int64_t)t0 * q.n * B : nullptr;
-  io.u_in = nullptr;
-  io.dt = dt;
-  io.seed = seed;
-  io.step0 = step0 + 1 + (uint64_t)t0;  // Neurons.update after the (step0 + t + 1)-th Agent.update
-  io.agent_id0 = agent_id0;
-  const bool noisy = q.noise_state != nullptr;
-  uint8_t* const spikes = io.spikes;
-  if (noisy) io.spikes = nullptr;  // spikes are drawn on the final rates, after the noise pass
-  int rc = RIAB_EUNSUPPORTED;
-  switch (q.kind) {
-    case RIAB_POP_PLACE:
-      rc = riab_place_cells(env, &io, q.table, q.n, q.description, q.geometry, q.top_hat_width, s);
-      break;
-    case RIAB_POP_GRID: rc = riab_grid_cells(&io, q.table, q.n, q.description, q.f0, s); break;
-    case RIAB_POP_HDC: rc = riab_head_direction_cells(&io, q.table, q.n, s); break;
-    case RIAB_POP_SPEED:  // history["vel"]: the measured velocity rows
-      io.hd_x = row + (int64_t)RIAB_H_VEL_X * B;
-      io.hd_y = row + (int64_t)RIAB_H_VEL_Y * B;
-      rc = riab_speed_cell(&io, q.one_sigma_speed, s);
-      break;
-    case RIAB_POP_RANDOM_SPATIAL:
-      rc = riab_random_spatial_neurons(env, &io, q.table, q.n_anchors, q.targets, q.n, q.geometry, s);
-      break;
-    case RIAB_POP_BVC:
-      rc = riab_boundary_vector_cells_windowed(env, &io, q.test_dirs, q.ray_rden, q.K, q.table, q.vm_table, q.inv_norm, q.n,
-                                               q.egocentric, nullptr, q.cell_rows, q.windows, s);
-      break;
-    case RIAB_POP_OVC:
-      rc = riab_object_vector_cells(env, &io, q.objects, q.object_types, q.n_objects, q.table, q.n, q.walls_occlude,
-                                    q.egocentric, s);
-      break;
-    case RIAB_POP_FF: {
-      RiabFFInput in[RIAB_FF_MAX_INPUTS];
-      for (int l = 0; l < q.n_inputs; ++l) {
-        const RiabPopulation& src = pops[q.input_index[l]];  // (an earlier population: its rows of this chunk exist)
-        in[l].rates = src.rates_base + (int64_t)t0 * src.n * B;
-        in[l].wt = q.input_wt[l];
-        in[l].n_in = src.n;
-      }
-      rc = riab_feedforward(in, q.n_inputs, q.bias, q.n, tc, B, q.activation, q.act_params, io.rates, nullptr, s);
-      if (rc == RIAB_OK && io.spikes) rc = riab_spikes(&io, q.n, s);
-      break;
-    }
-    default: break;  // (velocity cells read the float64 state: they advance through a step plan)
-  }
-  if (rc) return rc;
-  if (noisy) {
-    rc = riab_neuron_noise(q.noise_state, io.rates, nullptr, q.n, B, tc, q.noise_theta_dt, q.noise_sigma_dt, seed,
-                           step0 + 1 + (uint64_t)t0, q.io.pop_id, agent_id0, s);
-    if (rc) return rc;
-    if (spikes) {
-      io.spikes = spikes;
-      rc = riab_spikes(&io, q.n, s);
-    }
-  }
-  return rc;
-}
-
-namespace riab {
-int ovc_object_limit();  // riab_ovc.hip: the most objects the vector-cell kernel's LDS staging holds (-1: no device)
+// rows [t0, t0 + tc) of population i from the trajectory rows of the same chunk: `tc` calls of Neurons.update on
+// successive rows (riab_plan.hip: launch_population_rows, which says what differs from a step plan's one-row launches)
+static int launch_pop_rows(const RiabSimulate* q, int i, int32_t t0, int32_t tc, hipStream_t s) {
+  riab::PopRows r = {};
+  r.env = q->env;
+  r.pops = q->pops;
+  r.index = i;
+  r.hist = q->hist + (int64_t)t0 * RIAB_HIST_ROWS * q->B;
+  r.hist_ld = (int64_t)RIAB_HIST_ROWS * q->B;
+  r.B = q->B;
+  r.T = tc;
+  r.rate_row = t0;
+  r.dt = (float)q->motion->dt;
+  r.seed = q->seed;
+  r.step0 = q->step0 + 1 + (uint64_t)t0;  // Neurons.update after the (step0 + t + 1)-th Agent.update
+  r.agent_id0 = q->agent_id0;
+  return riab::launch_population_rows(r, s, nullptr);
 }
 
 static int check_populations(const RiabPopulation* pops, int32_t n_pops, int32_t T) {
   for (int i = 0; i < n_pops; ++i) {
     const RiabPopulation& q = pops[i];
     if (q.n <= 0 || !q.rates_base || q.capacity_rows < T) return RIAB_EINVAL;
-    switch (q.kind) {
-      case RIAB_POP_PLACE: case RIAB_POP_GRID: case RIAB_POP_HDC: case RIAB_POP_SPEED: case RIAB_POP_RANDOM_SPATIAL:
-      case RIAB_POP_BVC: break;
-      case RIAB_POP_OVC: {  // refused here, before the trajectory kernel is in flight, not by the launch of a chunk
-        const int limit = riab::ovc_object_limit();
-        if (limit >= 0 && q.n_objects > limit) return RIAB_ETOOBIG;
-        break;
-      }
-      case RIAB_POP_FF:
-        if (q.n_inputs <= 0 || q.n_inputs > RIAB_FF_MAX_INPUTS) return RIAB_EINVAL;
-        for (int l = 0; l < q.n_inputs; ++l)
-          if (q.input_index[l] < 0 || q.input_index[l] >= i || pops[q.input_index[l]].capacity_rows < T) return RIAB_EINVAL;
-        break;
-      default: return RIAB_EUNSUPPORTED;  // (velocity cells read the float64 state: they advance through a step plan)
-    }
+    // (velocity and phase-precessing cells read the float64 state: they advance through a step plan)
+    if (q.kind < RIAB_POP_PLACE || q.kind > RIAB_POP_THETA_PLACE || q.kind == RIAB_POP_VELOCITY || q.kind == RIAB_POP_THETA_PLACE)
+      return RIAB_EUNSUPPORTED;
+    const int rc = riab::check_population(q, i);  // (refused before the trajectory kernel is in flight, not by a chunk's launch)
+    if (rc) return rc;
+    if (q.kind == RIAB_POP_FF)
+      for (int l = 0; l < q.n_inputs; ++l)
+        if (pops[q.input_index[l]].capacity_rows < T) return RIAB_EINVAL;
   }
   return RIAB_OK;
 }
@@ -640,7 +566,7 @@ extern "C" int riab_simulate(RiabStreamer* h, const RiabSimulate* q, riab_stream
     for (int32_t t0 = 0; t0 < T && !fail; t0 += 4096) {  // (time rows are a grid axis of the rate kernels)
       const int32_t tc = T - t0 < 4096 ? T - t0 : 4096;
       for (int i = 0; i < n_pops && !fail; ++i)
-        fail = launch_pop_rows(env, pops, i, q->hist, B, t0, tc, dt, q->seed, q->step0, q->agent_id0, main_s);
+        fail = launch_pop_rows(q, i, t0, tc, main_s);
     }
     return fail ? RIAB_EPARTIAL : RIAB_OK;
   }
@@ -832,7 +758,7 @@ extern "C" int riab_simulate(RiabStreamer* h, const RiabSimulate* q, riab_stream
       const int32_t tc = T - t0 < tail_piece ? T - t0 : tail_piece;
       fail = riab::launch_stream_gate(q->ctrl, h->started_total, n_traj, (uint32_t)q->step0 + (uint32_t)(t0 + tc),
                                       gate_limit(1u << 22), false, 0u, main_s);
-      if (!fail) fail = launch_pop_rows(env, pops, lead, q->hist, B, t0, tc, dt, q->seed, q->step0, q->agent_id0, main_s);
+      if (!fail) fail = launch_pop_rows(q, lead, t0, tc, main_s);
       h->last_launches += 2;
     }
     if (timed_lead && !pure) {
@@ -847,7 +773,7 @@ extern "C" int riab_simulate(RiabStreamer* h, const RiabSimulate* q, riab_stream
         const int32_t tc = T - t0 < rest_piece ? T - t0 : rest_piece;
         const bool timed = timing && i == q->timed_pop;
         if (timed) (void)hipEventRecord(h->pairs[2 * n_timed], main_s);
-        fail = launch_pop_rows(env, pops, i, q->hist, B, t0, tc, dt, q->seed, q->step0, q->agent_id0, main_s);
+        fail = launch_pop_rows(q, i, t0, tc, main_s);
         if (timed) {
           (void)hipEventRecord(h->pairs[2 * n_timed + 1], main_s);
           ++n_timed;
@@ -877,7 +803,7 @@ extern "C" int riab_simulate(RiabStreamer* h, const RiabSimulate* q, riab_stream
       h->last_launches += 1 + n_pops;
       for (int i = 0; i < n_pops && !fail; ++i) {
         if (timing && i == q->timed_pop) (void)hipEventRecord(h->pairs[2 * k], main_s);
-        fail = launch_pop_rows(env, pops, i, q->hist, B, t0, tc, dt, q->seed, q->step0, q->agent_id0, main_s);
+        fail = launch_pop_rows(q, i, t0, tc, main_s);
         if (timing && i == q->timed_pop) (void)hipEventRecord(h->pairs[2 * k + 1], main_s);
       }
       t0 += tc;

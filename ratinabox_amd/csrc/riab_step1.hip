@@ -37,6 +37,7 @@
 #include "riab_rate_cells.h"
 #include "riab_handover.h"
 #include "riab_task_world_kernel.h"  // (last: riab_task_kernel.h, which it includes, turns fp contraction off for its own code)
+#include "riab_launch.h"
 
 namespace riab {
 
@@ -1359,37 +1360,29 @@ int launch_step1(const AgentArgs& a, const RiabEnv* env, const Step1PopRef* refs
 // whose two stages this replaces together with the fused populations' launches
 // (`query`: nothing is launched; RIAB_OK when this plan's step has a kernel to be launched with)
 int launch_step1_task(const AgentArgs& a, const RiabEnv* env, const Step1PopRef* refs, int n_pops, uint64_t seed,
-                      uint64_t step_after, uint32_t* sync_words, uint32_t epoch, bool* walls_ready, int n_cus, const RiabTask* task,
-                      double* task_state, int64_t task_B, double t_env, double* reward_out, uint8_t* terminal_out, int32_t* diag,
-                      bool auto_reset, int32_t n_select, int32_t ordered, uint64_t task_seed, uint64_t counter, int32_t teleport,
-                      double* ep_log, int64_t ep_log_cap, int32_t* ep_count, double gv_scale, double* gv_x, double* gv_y,
-                      double* world, uint64_t* world_met, int32_t* world_cand, int32_t* world_ctl, hipStream_t s, bool query) {
+                      uint64_t step_after, uint32_t* sync_words, uint32_t epoch, bool* walls_ready, int n_cus, const TaskRun& t,
+                      hipStream_t s, bool query) {
   Step1Task tk = {};
-  int rc = fill_args(tk.a, env, task, task_state, task_B);
+  int mode;
+  const int rc = fill_task_run(tk.a, tk.r, &mode, t);  // (t.hist_x / hist_y are null: the writer patches the row it stores)
   if (rc) return rc;
-  if (task_B > a.B || !reward_out || !terminal_out || !diag || !sync_words) return RIAB_EINVAL;
-  if (world && (!world_met || !world_cand || !world_ctl || task_B > 0x7FFFFFFF)) return RIAB_EINVAL;
-  tk.world = world;  // (non-null: the lanes are the agents of ONE world)
-  tk.met = world_met;
-  tk.cand = world_cand;
-  tk.ctl = world_ctl;
-  if (auto_reset) {
-    double* const pos_x = a.state + (int64_t)RIAB_S_POS_X * a.B;
-    rc = fill_reset(tk.r, env, a.agent_id0, n_select, ordered, task_seed, counter, teleport, nullptr, nullptr, pos_x, pos_x + a.B,
-                    nullptr, nullptr, ep_log, ep_log_cap, ep_count);
-    if (rc) return rc;
-    tk.r.pos_x = tk.r.pos_y = nullptr;  // (the writer stores the position the lane hands back, with the state)
-  }
-  tk.t_env = t_env;
-  tk.reward_out = reward_out;
-  tk.terminal_out = terminal_out;
-  tk.gv_scale = gv_scale;
-  tk.gv_x = gv_x;
-  tk.gv_y = gv_y;
-  tk.diag = diag;
+  if (t.task_B > a.B || !sync_words) return RIAB_EINVAL;
+  if (t.world && (!t.world_met || !t.world_cand || !t.world_ctl || t.task_B > 0x7FFFFFFF)) return RIAB_EINVAL;
+  tk.world = t.world;  // (non-null: the lanes are the agents of ONE world)
+  tk.met = t.world_met;
+  tk.cand = t.world_cand;
+  tk.ctl = t.world_ctl;
+  tk.r.pos_x = tk.r.pos_y = nullptr;  // (the writer stores the position the lane hands back, with the state)
+  tk.t_env = t.t_env;
+  tk.reward_out = t.reward_out;
+  tk.terminal_out = t.terminal_out;
+  tk.gv_scale = t.gv_scale;
+  tk.gv_x = t.gv_x;
+  tk.gv_y = t.gv_y;
+  tk.diag = t.diag;
   tk.mail = sync_words + RIAB_STEP1_SYNC_MAIL_AT(a.B);
-  const int mode = 1 | (auto_reset ? 2 : 0) | (gv_x ? 4 : 0) | (world ? 8 : 0);
-  return launch_step1_impl(a, env, refs, n_pops, seed, step_after, sync_words, epoch, walls_ready, n_cus, s, &tk, mode, query);
+  return launch_step1_impl(a, env, refs, n_pops, seed, step_after, sync_words, epoch, walls_ready, n_cus, s, &tk,
+                           mode | (t.world ? 8 : 0), query);
 }
 
 // The compute units a stream's workgroups land on, counted: every one-wave workgroup of a grid that fills any device

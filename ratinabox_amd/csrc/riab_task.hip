@@ -1,33 +1,24 @@
 // Batched TaskEnvironment on gfx950: the C ABI entry points of the task kernel (riab_task_kernel.h).
 #include "riab_task_kernel.h"
+#include "riab_launch.h"
 
 namespace riab {
 
 // The step plan's fused launch: TaskEnvironment.step, reset of the lanes that became terminal (when
 // auto_reset) and the scripted action of the next step (when gv_x is given) in one kernel.
-int launch_task_fused(const RiabEnv* env, const RiabTask* task, double* task_state, double* pos_x, double* pos_y, int64_t B,
-                      double t_env, double* reward_out, uint8_t* terminal_out, int32_t* diag, bool auto_reset,
-                      int64_t agent_id0, int32_t n_select, int32_t ordered, uint64_t seed, uint64_t counter,
-                      int32_t teleport, float* hist_x, float* hist_y, double* ep_log, int64_t ep_log_cap,
-                      int32_t* ep_count, double gv_scale, double* gv_x, double* gv_y, hipStream_t s) {
+int launch_task_fused(const TaskRun& t, hipStream_t s) {
   TaskArgs a;
-  int rc = fill_args(a, env, task, task_state, B);
+  ResetArgs r;
+  int mode;
+  const int rc = fill_task_run(a, r, &mode, t);
   if (rc) return rc;
-  if (!pos_x || !pos_y || !reward_out || !terminal_out || !diag) return RIAB_EINVAL;
-  ResetArgs r = {};
-  if (auto_reset) {
-    rc = fill_reset(r, env, agent_id0, n_select, ordered, seed, counter, teleport, nullptr, nullptr, pos_x, pos_y, hist_x,
-                    hist_y, ep_log, ep_log_cap, ep_count);
-    if (rc) return rc;
-  }
-  const dim3 grid((unsigned)((B + 63) / 64)), block(64);
-  const bool gv = gv_x != nullptr;
-#define RIAB_TASK_LAUNCH(MODE)                                                                                  \
-  hipLaunchKernelGGL(task_kernel<MODE>, grid, block, 0, s, a, r, pos_x, pos_y, t_env, reward_out, terminal_out, \
-                     (const uint8_t*)nullptr, gv_scale, gv_x, gv_y, diag)
-  if (auto_reset && gv) RIAB_TASK_LAUNCH(7);
-  else if (auto_reset) RIAB_TASK_LAUNCH(3);
-  else if (gv) RIAB_TASK_LAUNCH(5);
+  const dim3 grid((unsigned)((t.task_B + 63) / 64)), block(64);
+#define RIAB_TASK_LAUNCH(MODE)                                                                                \
+  hipLaunchKernelGGL(task_kernel<MODE>, grid, block, 0, s, a, r, t.pos_x, t.pos_y, t.t_env, t.reward_out,       \
+                     t.terminal_out, (const uint8_t*)nullptr, t.gv_scale, t.gv_x, t.gv_y, t.diag)
+  if (mode == 7) RIAB_TASK_LAUNCH(7);
+  else if (mode == 3) RIAB_TASK_LAUNCH(3);
+  else if (mode == 5) RIAB_TASK_LAUNCH(5);
   else RIAB_TASK_LAUNCH(1);
 #undef RIAB_TASK_LAUNCH
   return (int)hipGetLastError();

@@ -24,6 +24,7 @@
 //     (step1_task_kernel, riab_step1.hip).
 #include "riab_device.h"
 #include "riab_handover.h"
+#include "riab_launch.h"
 
 // The reward recursions are compared bit for bit with the reference's float64 python arithmetic:
 // no fused multiply-adds in this file.
@@ -751,6 +752,23 @@ static int fill_reset(ResetArgs& r, const RiabEnv* env, int64_t agent_id0, int32
   r.ep_log = ep_log;
   r.ep_log_cap = ep_log_cap;
   r.ep_count = ep_count;
+  return RIAB_OK;
+}
+
+// What the step plan's launchers of a task step share (launch_task_fused, launch_motion_task, launch_step1_task): the
+// checks, the kernel's task and reset arguments from the record, and the task kernel's MODE: 1 the step | 2 the reset of
+// the lanes that became terminal | 4 the coming step's scripted action.
+static int fill_task_run(TaskArgs& a, ResetArgs& r, int* mode, const TaskRun& t) {
+  int rc = fill_args(a, t.env, &t.task, t.task_state, t.task_B);
+  if (rc) return rc;
+  if (!t.pos_x || !t.pos_y || !t.reward_out || !t.terminal_out || !t.diag) return RIAB_EINVAL;
+  r = {};
+  if (t.auto_reset) {
+    rc = fill_reset(r, t.env, t.agent_id0, t.n_select, t.ordered, t.seed, t.counter, t.teleport, nullptr, nullptr, t.pos_x,
+                    t.pos_y, t.hist_x, t.hist_y, t.ep_log, t.ep_log_cap, t.ep_count);
+    if (rc) return rc;
+  }
+  *mode = 1 | (t.auto_reset ? 2 : 0) | (t.gv_x ? 4 : 0);
   return RIAB_OK;
 }
 

@@ -19,6 +19,7 @@
 // Float64 like the reference; contraction off (riab_task_kernel.h).
 #include "riab_agent_kernel.h"  // (the motion step: the plan launches it and the world step as one kernel)
 #include "riab_task_world_kernel.h"  // (after it: its headers turn fp contraction off for their own code)
+#include "riab_launch.h"
 
 #pragma clang fp contract(off)
 
@@ -159,15 +160,14 @@ static int fill_world_args(TaskArgs& a, const RiabEnv* env, const RiabTask* task
 }
 
 // the step plan's motion + world step launch (riab_plan.hip); `ma`: the motion step of the plan's (padded) batch
-int launch_motion_world(const AgentArgs& ma, const RiabEnv* env, const RiabTask* task, double* task_state, double* world,
-                        const double* pos_x, const double* pos_y, int64_t task_B, double t_env, double* reward_out,
-                        uint8_t* terminal_out, uint64_t* met, int32_t* cand, int32_t* ctl, int32_t* diag, hipStream_t s) {
+int launch_motion_world(const AgentArgs& ma, const TaskRun& t, hipStream_t s) {
   TaskArgs a;
-  const int rc = fill_world_args(a, env, task, task_state, world, task_B);
+  const int rc = fill_world_args(a, t.env, &t.task, t.task_state, t.world, t.task_B);
   if (rc) return rc;
-  if (!pos_x || !pos_y || !reward_out || !terminal_out || !met || !cand || !ctl || !diag) return RIAB_EINVAL;
-  hipLaunchKernelGGL(motion_world_kernel, dim3((unsigned)((ma.B + 63) / 64)), dim3(64), 0, s, ma, a, world, pos_x, pos_y, t_env,
-                     reward_out, terminal_out, met, cand, ctl, diag);
+  if (!t.pos_x || !t.pos_y || !t.reward_out || !t.terminal_out || !t.world_met || !t.world_cand || !t.world_ctl || !t.diag)
+    return RIAB_EINVAL;
+  hipLaunchKernelGGL(motion_world_kernel, dim3((unsigned)((ma.B + 63) / 64)), dim3(64), 0, s, ma, a, t.world, t.pos_x, t.pos_y,
+                     t.t_env, t.reward_out, t.terminal_out, t.world_met, t.world_cand, t.world_ctl, t.diag);
   return (int)hipGetLastError();
 }
 

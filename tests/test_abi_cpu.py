@@ -106,6 +106,22 @@ def test_step_plan_validation_without_gpu(L):
     assert L.lib.riab_plan_add(h, pop) == -1
     pop.kind = L.POP_KINDS["place"]
     assert L.lib.riab_plan_add(h, pop) == 0
+    for kind in (-1, 10):  # (one below the first kind, one beyond the last)
+        pop.kind = kind
+        assert L.lib.riab_plan_add(h, pop) == L.EINVAL
+    ff = L.RiabPopulation()
+    ff.kind, ff.n, ff.bias, ff.input_wt[0] = L.POP_KINDS["ff"], 4, 16, 16
+    for n_inputs in (0, 9):
+        ff.n_inputs = n_inputs
+        assert L.lib.riab_plan_add(h, ff) == L.EINVAL
+    ff.n_inputs, ff.input_index[0] = 1, 1  # (the plan holds one population: an input must be in it already)
+    assert L.lib.riab_plan_add(h, ff) == L.EINVAL
+    ff.input_index[0], ff.bias = 0, None
+    assert L.lib.riab_plan_add(h, ff) == L.EINVAL
+    ff.bias, ff.input_wt[0] = 16, None
+    assert L.lib.riab_plan_add(h, ff) == L.EINVAL
+    ff.input_wt[0] = 16
+    assert L.lib.riab_plan_add(h, ff) == 1
     assert L.lib.riab_plan_set_population_history(h, 3, C.c_void_p(16), None, 4) == -1
     assert L.lib.riab_plan_set_population_history(h, 0, C.c_void_p(16), None, 2) == 0
     assert L.lib.riab_plan_set_agent_history(h, C.c_void_p(16), 8) == 0

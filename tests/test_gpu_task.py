@@ -561,6 +561,43 @@ def test_one_launch_task_step_equals_the_two_launch_plan(riab, case):
         assert jumps > 0.05
 
 
+def test_task_plan_with_motion_and_task_launched_apart(riab):
+    """A task plan with option `fused_task` = 0 launches Agent.update and the rest of TaskEnvironment.step (+ auto-reset
+    with teleport, + the next scripted action) as two kernels; with 1, as one.  64 agents: one wave, no one-launch step on
+    either side.  Same positions, rates, rewards, terminal flags and episode log, bit for bit; the launch counts are the
+    step's: [motion + task | motion, task] + the rate kernel per step, + the launch of the plan's first scripted action."""
+    T, speed = 12, 11.0 * 0.08
+
+    def run(fused_task):
+        old = riab._lib.set_option("fused_task", fused_task)
+        try:
+            env, Ag, P = _task_world(riab, 11, B=64, n=8, teleport=True, order="nonsequential", delay=0.0, radius=0.3)
+            plan = env.make_step_plan(auto_reset=True, scripted_speed=speed)
+            rews, terms = [], []
+            for k in range(T):
+                plan.step(1)
+                rews.append(env.get_reward().clone())
+                terms.append(env.terminal.clone())
+            torch.cuda.synchronize()
+            out = dict(rew=torch.stack(rews).cpu().numpy(), term=torch.stack(terms).cpu().numpy(),
+                       state=Ag.state_tensor[:, :Ag.n_agents].cpu().numpy(), ts=env.task_state.cpu().numpy(),
+                       traj=Ag.get_history_tensor().cpu().numpy(), fr=P.get_history_tensors()[0].cpu().numpy(),
+                       action=plan._actions[:, :Ag.n_agents].cpu().numpy())
+            return out, dict(env.episodes), dict(env.diagnostics), env.t, plan.info()
+        finally:
+            riab._lib.set_option("fused_task", old)
+
+    a, ep_a, d_a, t_a, info_a = run(1)
+    b, ep_b, d_b, t_b, info_b = run(0)
+    assert info_a["fused_steps"] == 0 and info_b["fused_steps"] == 0
+    assert info_a["launches"] == 2 * T + 1, info_a
+    assert info_b["launches"] == 3 * T + 1, info_b
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    assert ep_a == ep_b and d_a == d_b and t_a == t_b
+    assert a["term"].any() and len(ep_a["episode"]) > 0   # lanes ended an episode and were reset (the reset logs it)
+
+
 @pytest.mark.parametrize("batch,radius,all_spikes", [(1, None, False), (7, None, False), (1, 0.3, True), (3, 0.35, True)])
 def test_one_launch_task_step_with_other_populations_and_batches(riab, batch, radius, all_spikes):
     """The store-bound populations ride in the task step's kernel, the others (boundary vector cells) follow as their own
