@@ -268,6 +268,14 @@ enum { RIAB_GC_RECTIFIED = 0, RIAB_GC_SHIFTED = 1 };
 int riab_grid_cells(const RiabRateIO* io, const float* table, int32_t n, int32_t description,
                     float f0, riab_stream_t stream);
 
+/* contribs.PlaneWaveNeurons.get_state (contribs/PlaneWaveNeurons.py:63-91): one cosine per cell,
+ *   rate = (cos(phi) + 1) / 2, phi = (2 pi / wavescale) * ((phase_offset - p) . w),
+ * scaled to [min_fr, max_fr].  table device float32 [n][3] = (a, bx, by) with the phase in
+ * revolutions, phi/2pi = a - (x*bx + y*by): a = frac((phase_offset . w) / wavescale),
+ * (bx, by) = w / wavescale — one term of the GridCells table — built on the host in float64
+ * and rounded once. */
+int riab_plane_wave_neurons(const RiabRateIO* io, const float* table, int32_t n, riab_stream_t stream);
+
 /* HeadDirectionCells.get_state, 2D (Neurons.py:2421-2485): von Mises of
  * utils.get_angle(head_direction).  table device float32 [n][3] = (cosine and sine of the
  * preferred angle, log2(e)/sigma^2) per cell.  Needs io->hd_x / hd_y. */
@@ -419,7 +427,10 @@ int riab_feedforward(const RiabFFInput* inputs, int32_t n_inputs, const float* b
  * row cursors, RNG counters and pointers are kept in C++, every kernel of every step is enqueued on
  * `stream`, nothing is allocated or synchronised. */
 enum { RIAB_POP_PLACE = 0, RIAB_POP_GRID = 1, RIAB_POP_HDC = 2, RIAB_POP_BVC = 3, RIAB_POP_OVC = 4, RIAB_POP_FF = 5,
-       RIAB_POP_VELOCITY = 6, RIAB_POP_SPEED = 7, RIAB_POP_RANDOM_SPATIAL = 8, RIAB_POP_THETA_PLACE = 9 };
+       RIAB_POP_VELOCITY = 6, RIAB_POP_SPEED = 7, RIAB_POP_RANDOM_SPATIAL = 8, RIAB_POP_THETA_PLACE = 9,
+       /* 10 is not assigned and stays refused (RIAB_EINVAL): callers written against ABI 10 / 11 probe "the first kind
+        * past the last one" with it and expect the refusal */
+       RIAB_POP_PLANE_WAVE = 11 };
 #define RIAB_FF_MAX_INPUTS 8
 
 typedef struct RiabPopulation {
@@ -429,7 +440,7 @@ typedef struct RiabPopulation {
   float* rates_base;         /* device float32 [capacity_rows][n][B] history chunk */
   uint8_t* spikes_base;      /* device uint8 [capacity_rows][n][B] or NULL */
   int64_t capacity_rows;     /* 0: rates_base is a single row overwritten every step */
-  const float* table;        /* the population's cell table (as in its own entry point) */
+  const float* table;        /* the population's cell table (as in its own entry point); all a plane-wave population needs */
   int32_t description;       /* place / grid */
   int32_t geometry;          /* place */
   float top_hat_width;       /* place */
@@ -750,7 +761,7 @@ int riab_plan_set_task_world(RiabPlan* plan, double* world, uint64_t* met_scratc
  * T calls of riab_agent_step(T = 1) each followed by the populations' own entry points.
  *
  * Forms of the rate stage, chosen by the call (riab_streamer_last_form):
- *  - a "lead" population — kind RIAB_POP_PLACE (not one_hot) / RIAB_POP_GRID / RIAB_POP_HDC without OU noise, B a
+ *  - a "lead" population — kind RIAB_POP_PLACE (not one_hot) / RIAB_POP_GRID / RIAB_POP_HDC / RIAB_POP_PLANE_WAVE without OU noise, B a
  *    multiple of 256, T <= POLL_MAX — is served by ONE kernel for all its rows whose waves each wait until the 256 agents
  *    of the wave have been stepped past their row (runs of more than 2048 rows: the first HEAD_ROWS rows; the others by
  *    the population's ordinary kernel, 512 rows per launch behind a progress gate);

@@ -121,7 +121,7 @@ TW_N_GOALS, TW_DELAYED, TW_PAD_START, TW_EPISODE, TW_EP_START, TW_EP_ANY_ENDED, 
 TW_TERMINAL, TW_GOAL_LIST, TW_ROWS = 7, 8, 24
 
 POP_KINDS = {"place": 0, "grid": 1, "hdc": 2, "bvc": 3, "ovc": 4, "ff": 5, "velocity": 6, "speed": 7, "random_spatial": 8,
-             "theta_place": 9}
+             "theta_place": 9, "plane_wave": 11}   # (10 is not assigned: riab_hip.h)
 THETA_NONE, THETA_BEHIND, THETA_AHEAD = 0, 1, 2                          # riab_hip.h RIAB_THETA_*
 THETA_DIAG_BEHIND, THETA_DIAG_AHEAD, THETA_DIAG_ROLLOUT, THETA_DIAG_FAR = range(4)
 EINVAL = -1
@@ -172,6 +172,7 @@ PROTOTYPES = {
     "riab_place_cells": (C.c_int, [C.POINTER(RiabEnv), C.POINTER(RiabRateIO), C.c_void_p, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_float, C.c_void_p]),
     "riab_grid_cells": (C.c_int, [C.POINTER(RiabRateIO), C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "riab_plane_wave_neurons": (C.c_int, [C.POINTER(RiabRateIO), C.c_void_p, C.c_int32, C.c_void_p]),
     "riab_head_direction_cells": (C.c_int, [C.POINTER(RiabRateIO), C.c_void_p, C.c_int32, C.c_void_p]),
     "riab_env_pairwise": (C.c_int, [C.POINTER(RiabEnv), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -6,5 +6,6 @@ the reference's way —
     from ratinabox_amd.contribs.SuccessorFeatures import SuccessorFeatures
     from ratinabox_amd.contribs.PhasePrecessingPlaceCells import PhasePrecessingPlaceCells
     from ratinabox_amd.contribs.SubAgent import SubAgent, ThetaSequenceAgent, ShiftAgent, UnrelatedAgent
+    from ratinabox_amd.contribs.PlaneWaveNeurons import PlaneWaveNeurons
 """
-__all__ = ["TaskEnvironment", "ValueNeuron", "SuccessorFeatures", "PhasePrecessingPlaceCells", "SubAgent"]
+__all__ = ["TaskEnvironment", "ValueNeuron", "SuccessorFeatures", "PhasePrecessingPlaceCells", "SubAgent", "PlaneWaveNeurons"]

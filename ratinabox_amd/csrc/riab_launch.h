@@ -62,6 +62,10 @@ struct PopRows {
 // riab_plan.hip
 int launch_population_rows(const PopRows& r, hipStream_t s, int64_t* launches);
 int check_population(const RiabPopulation& q, int n_before);
+// an assigned RIAB_POP_* value (riab_hip.h: 10 is not one)
+inline bool population_kind_known(int kind) {
+  return (kind >= RIAB_POP_PLACE && kind <= RIAB_POP_THETA_PLACE) || kind == RIAB_POP_PLANE_WAVE;
+}
 
 // riab_agent.hip
 int launch_agent_pub(const AgentArgs& a, hipStream_t s, bool* state_published);

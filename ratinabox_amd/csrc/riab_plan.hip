@@ -329,12 +329,13 @@ int riab::check_population(const RiabPopulation& q, int n_before) {
 }
 
 extern "C" int riab_plan_add(RiabPlan* p, const RiabPopulation* pop) {
-  if (!p || !pop || pop->n <= 0 || pop->kind < RIAB_POP_PLACE || pop->kind > RIAB_POP_THETA_PLACE) return RIAB_EINVAL;
+  if (!p || !pop || pop->n <= 0 || !riab::population_kind_known(pop->kind)) return RIAB_EINVAL;
   // (a plan that could not take its first step is refused when it is recorded; feed-forward only: an input must already
   // be in the plan)
   const int rc = riab::check_population(*pop, (int)p->pops.size());
   if (rc) return rc;
   if (pop->kind == RIAB_POP_THETA_PLACE && (!pop->table || !(pop->theta_freq > 0.0) || !(pop->kappa >= 0.0))) return RIAB_EINVAL;
+  if (pop->kind == RIAB_POP_PLANE_WAVE && !pop->table) return RIAB_EINVAL;
   if (pop->kind == RIAB_POP_FF) {
     if (!pop->bias) return RIAB_EINVAL;
     for (int l = 0; l < pop->n_inputs; ++l)
@@ -483,6 +484,7 @@ int riab::launch_population_rows(const PopRows& r, hipStream_t s, int64_t* launc
     case RIAB_POP_PLACE: rc = riab_place_cells(env, &io, q.table, q.n, q.description, q.geometry, q.top_hat_width, s); break;
     case RIAB_POP_GRID: rc = riab_grid_cells(&io, q.table, q.n, q.description, q.f0, s); break;
     case RIAB_POP_HDC: rc = riab_head_direction_cells(&io, q.table, q.n, s); break;
+    case RIAB_POP_PLANE_WAVE: rc = riab_plane_wave_neurons(&io, q.table, q.n, s); break;
     case RIAB_POP_VELOCITY:  // Agent.velocity: rows of the float64 state, not of the history record
       if (!r.state) break;
       rc = riab_velocity_cells(&io, q.table, q.n, q.one_sigma_speed, r.state + RIAB_S_VEL_X * B, r.state + RIAB_S_VEL_Y * B, s);

@@ -306,6 +306,44 @@ struct GridCell {
   }
 };
 
+// ---- contribs.PlaneWaveNeurons (reference contribs/PlaneWaveNeurons.py:63-91) ------------------------------------
+// One cosine per cell: rate = (cos(phi) + 1) / 2, phi / 2 pi = ((offset - p) . w) / wavescale = a - (x*bx + y*by), the
+// table row (a, bx, by) in revolutions exactly as one term of GridCells'.  One fraction and one v_cos_f32 per rate.
+struct PlaneWaveCell {
+  typedef PosQuad Pos;
+  static constexpr int LDS_DOUBLES = 1;
+  __device__ __forceinline__ void stage(double*) {}
+  const float* tab;  // [n][3] = (a, bx, by)
+  __device__ __forceinline__ Pos load(const RateArgs& a, int64_t off) const {
+    return Pos{ldv4(a.pos_x + off), ldv4(a.pos_y + off)};
+  }
+  __device__ __forceinline__ Pos load_agent(const RateArgs& a, int64_t off) const {
+    return Pos{ld_agent_v4f(a.pos_x + off), ld_agent_v4f(a.pos_y + off)};
+  }
+  __device__ __forceinline__ Pos from_rows(v4f x, v4f y, v4f, v4f) const { return Pos{x, y}; }
+  static constexpr bool NEEDS_HD = false;
+  static constexpr bool NEEDS_POS = true;
+  // two agents per instruction, as GridCell::two (v_pk_mul / v_pk_fma / v_pk_add around one fraction and one v_cos each).
+  // Contraction is off: the product y*by, the FMA and the subtraction are three roundings in every kernel that
+  // evaluates the functor (the wide, generic and row-following kernels are compared bit for bit).
+  __device__ __forceinline__ v2f two(const float* p, v2f x, v2f y) const {
+#pragma clang fp contract(off)
+    const v2f p0 = {p[0], p[0]}, p1 = {p[1], p[1]}, p2 = {p[2], p[2]};
+    v2f rev = p0 - __builtin_elementwise_fma(x, p1, y * p2);
+    rev.x -= floorf(rev.x);  // the fraction: keep the hardware cosine in its accurate range
+    rev.y -= floorf(rev.y);
+    const v2f c = {__builtin_amdgcn_cosf(rev.x), __builtin_amdgcn_cosf(rev.y)};
+    return __builtin_elementwise_fma(v2f{0.5f, 0.5f}, c, v2f{0.5f, 0.5f});
+  }
+  static constexpr int NP = 3;
+  static constexpr int CPB = 4;
+  __device__ __forceinline__ v4f eval(const float* p, const Pos& P) const {
+    const v2f lo = two(p, v2f{P.x.x, P.x.y}, v2f{P.y.x, P.y.y});
+    const v2f hi = two(p, v2f{P.x.z, P.x.w}, v2f{P.y.z, P.y.w});
+    return v4f{lo.x, lo.y, hi.x, hi.y};
+  }
+};
+
 // ---- HeadDirectionCells / VelocityCells / SpeedCell ------------------------------------------
 // (reference Neurons.py:2466-2483, 2577-2583, 2632-2651; utils.py:231-273, 441-457)
 // MODE 0: von Mises of utils.get_angle(head direction).

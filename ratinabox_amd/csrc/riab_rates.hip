@@ -681,7 +681,7 @@ static int launch_stream_cell(const RateArgs& a, const Cell& cell, const StreamL
   return (int)hipGetLastError();
 }
 
-// f(functor) for a population of the streamed kinds (place, grid, head direction)
+// f(functor) for a population of the streamed kinds (place, grid, head direction, plane wave)
 template <class F>
 static int visit_stream_cell(const RiabEnv* env, const RiabPopulation* pop, F&& f) {
   switch (pop->kind) {
@@ -693,6 +693,7 @@ static int visit_stream_cell(const RiabEnv* env, const RiabPopulation* pop, F&& 
       });
     case RIAB_POP_GRID: return visit_grid_desc(pop->description, pop->table, pop->f0, f);
     case RIAB_POP_HDC: return f(HDCell<0>{pop->table, 0.0f, nullptr, nullptr});
+    case RIAB_POP_PLANE_WAVE: return f(PlaneWaveCell{pop->table});
     default: return RIAB_EUNSUPPORTED;
   }
 }
@@ -707,7 +708,8 @@ int stream_supported(const RiabEnv* env, const RiabPopulation* pop, int64_t B) {
       if (place_geometry_refused(env, pop->geometry)) return RIAB_EUNSUPPORTED;
       return pop->table ? RIAB_OK : RIAB_EINVAL;
     case RIAB_POP_GRID:
-    case RIAB_POP_HDC: return pop->table ? RIAB_OK : RIAB_EINVAL;
+    case RIAB_POP_HDC:
+    case RIAB_POP_PLANE_WAVE: return pop->table ? RIAB_OK : RIAB_EINVAL;
     default: return RIAB_EUNSUPPORTED;
   }
 }
@@ -868,6 +870,13 @@ extern "C" int riab_grid_cells(const RiabRateIO* io, const float* table, int32_t
   const int rc = check_io(io, n, true, false);
   if (rc) return rc;
   return visit_grid_desc(description, table, f0, [&](const auto& c) { return launch_rate(io, n, c, (hipStream_t)stream); });
+}
+
+extern "C" int riab_plane_wave_neurons(const RiabRateIO* io, const float* table, int32_t n, riab_stream_t stream) {
+  if (!table) return RIAB_EINVAL;
+  const int rc = check_io(io, n, true, false);
+  if (rc) return rc;
+  return launch_rate(io, n, PlaneWaveCell{table}, (hipStream_t)stream);
 }
 
 extern "C" int riab_head_direction_cells(const RiabRateIO* io, const float* table, int32_t n,

@@ -440,7 +440,7 @@ static int check_populations(const RiabPopulation* pops, int32_t n_pops, int32_t
     const RiabPopulation& q = pops[i];
     if (q.n <= 0 || !q.rates_base || q.capacity_rows < T) return RIAB_EINVAL;
     // (velocity and phase-precessing cells read the float64 state: they advance through a step plan)
-    if (q.kind < RIAB_POP_PLACE || q.kind > RIAB_POP_THETA_PLACE || q.kind == RIAB_POP_VELOCITY || q.kind == RIAB_POP_THETA_PLACE)
+    if (!riab::population_kind_known(q.kind) || q.kind == RIAB_POP_VELOCITY || q.kind == RIAB_POP_THETA_PLACE)
       return RIAB_EUNSUPPORTED;
     const int rc = riab::check_population(q, i);  // (refused before the trajectory kernel is in flight, not by a chunk's launch)
     if (rc) return rc;

@@ -12,7 +12,7 @@ trace under `torch.compile(fullgraph=True)` and FakeTensorMode.  Layouts are the
 is the last (fastest) one and must be a multiple of 4 (pad; padding columns are computed like any other).
 
 Functional operators (return a new tensor)
-    place_cells, grid_cells, head_direction_cells, boundary_vector_cells   rates float32 (n, P)
+    place_cells, grid_cells, plane_wave_neurons, head_direction_cells, boundary_vector_cells   rates float32 (n, P)
     spikes                                                              uint8 (T, n, B) from rates (T, n, B)
     feedforward                                                         float32 (T, n_out, B)
 In-place operators
@@ -126,6 +126,22 @@ def grid_cells(pos: Tensor, table: Tensor, description: int, f0: float, min_fr: 
     io = _io(pos, None, P, out, min_fr, max_fr)
     _L.check(_L.lib.riab_grid_cells(io, _L.ptr(table), n, int(description), float(f0), _L.current_stream()),
              "riab_grid_cells")
+    return out
+
+
+# ---- contribs.PlaneWaveNeurons -----------------------------------------------------------------------------------
+@_register("plane_wave_neurons(Tensor pos, Tensor table, float min_fr, float max_fr) -> Tensor",
+           lambda pos, table, min_fr, max_fr: pos.new_empty((table.shape[0], pos.shape[1])))
+def plane_wave_neurons(pos: Tensor, table: Tensor, min_fr: float, max_fr: float) -> Tensor:
+    """contribs.PlaneWaveNeurons.get_state (riab_plane_wave_neurons).  pos float32 (2, P); table float32 (n, 3) = (a, bx, by),
+    the phase in revolutions a - (x bx + y by), see include/riab_hip.h.  Returns rates float32 (n, P)."""
+    P = _rows(pos, 2, "pos")
+    n = int(table.shape[0])
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 3 or not table.is_contiguous():
+        raise ValueError("table must be a contiguous float32 tensor (n, 3) = (a, bx, by)")
+    out = torch.empty((n, P), dtype=torch.float32, device=pos.device)
+    io = _io(pos, None, P, out, min_fr, max_fr)
+    _L.check(_L.lib.riab_plane_wave_neurons(io, _L.ptr(table), n, _L.current_stream()), "riab_plane_wave_neurons")
     return out
 
 
