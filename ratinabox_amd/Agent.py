@@ -287,7 +287,7 @@ class Agent:
 
     def _upload(self, row, value):
         """Host edit of a state attribute: one value (broadcast to every agent) or one row per agent."""
-        if self._plan is not None and self._plan.__class__ is _AutoStepper:
+        if self._plan is not None and self._plan.serves_updates:
             self._plan.close()  # (the populations must now read the edited float64 state, which the eager path does)
         self._last_row = None  # the fp32 row the rate kernels read no longer mirrors the state
         width = 2 if row in (_L.S_POS_X, _L.S_VEL_X, _L.S_MVEL_X, _L.S_HD_X) else 1
@@ -426,7 +426,7 @@ class Agent:
         if (dt is None or dt == self.dt) and not kwargs and self._auto_enabled and \
                 (not self.use_imported_trajectory or (self.interpolate and drift_velocity is None)):
             st = self._plan
-            if st is not None and st.__class__ is _AutoStepper:
+            if st is not None and st.serves_updates:
                 if st.step_agent(drift_velocity, drift_to_random_strength_ratio):
                     return
                 st.close()

@@ -123,47 +123,34 @@ class Neurons:
         """This population as the ABI's RiabPopulation (for a step plan); keeps its tables alive.
         `plan_index`: {Neurons object: index in the plan} of the populations recorded before this one
         (what a FeedForwardLayer's inputs are looked up in)."""
-        if not isinstance(self, FeedForwardLayer):
-            # (the descriptor only changes when a table was rebuilt: simulate() of a short run asks for it every time,
-            # and building the ctypes struct costs ~50 us)
-            f = self._call(None, None)
-            vals = tuple(f.values())
-            hit = self.__dict__.get("_pop_cache")
-            if hit is not None and self.noise_std == 0 and hit[1] == (float(self.min_fr), float(self.max_fr)) and \
-                    len(hit[0]) == len(vals) and all(a is b if torch.is_tensor(a) else a == b for a, b in zip(hit[0], vals)):
-                return hit[2]
+        # (the descriptor only changes when a table was rebuilt: simulate() of a short run asks for it every time,
+        # and building the ctypes struct costs ~50 us)
+        f = self._call(None, None)
+        vals = tuple(f.values())
+        hit = self.__dict__.get("_pop_cache")
+        if hit is not None and self.noise_std == 0 and hit[1] == (float(self.min_fr), float(self.max_fr)) and \
+                len(hit[0]) == len(vals) and all(a is b if torch.is_tensor(a) else a == b for a, b in zip(hit[0], vals)):
+            return hit[2]
+        pop = self._population_header()
+        pop.kind = f["kind"]
+        self._plan_tables = [v for v in f.values() if torch.is_tensor(v)]
+        for k, v in f.items():
+            if k != "kind":
+                setattr(pop, k, v.data_ptr() if torch.is_tensor(v) else v)
+        if self.noise_std == 0:
+            self.__dict__["_pop_cache"] = (vals, (float(self.min_fr), float(self.max_fr)), pop)
+        return self._population_noise(pop)
+
+    def _population_header(self):
+        """A RiabPopulation with what every kind carries: the size, the rate bounds, the RNG stream."""
         pop = _L.RiabPopulation()
         pop.n = int(self.n)
         pop.io.min_fr, pop.io.max_fr, pop.io.pop_id = float(self.min_fr), float(self.max_fr), int(self.pop_id)
-        if isinstance(self, FeedForwardLayer):
-            entries = list(self.inputs.values())
-            if len(entries) > 8:
-                raise ValueError("a FeedForwardLayer in a step plan takes at most 8 input layers")
-            pop.kind, pop.n_inputs = _L.POP_KINDS["ff"], len(entries)
-            keep = []
-            for l, e in enumerate(entries):
-                if plan_index is None or e["layer"] not in plan_index:
-                    raise NotImplementedError(f"input layer {e['layer'].name} must be recorded in the plan before "
-                                              f"{self.name} (recurrent inputs advance through update())")
-                wt = self._device_weights(e)
-                pop.input_index[l], pop.input_wt[l] = plan_index[e["layer"]], wt.data_ptr()
-                keep.append(wt)
-            bias = np.asarray(self.biases, dtype=np.float32).reshape(-1)
-            bias_t = self._tables((bias,), lambda: torch.from_numpy(bias.copy()).to(self._device))
-            act, pars = self._activation()
-            pop.bias, pop.activation, pop.rates_prime = bias_t.data_ptr(), act, self._rates_prime.data_ptr()
-            for i in range(4):
-                pop.act_params[i] = pars[i]
-            self._plan_tables = keep + [bias_t]
-        else:
-            pop.kind = f["kind"]
-            self._plan_tables = [v for v in f.values() if torch.is_tensor(v)]
-            for k, v in f.items():
-                if k != "kind":
-                    setattr(pop, k, v.data_ptr() if torch.is_tensor(v) else v)
-            if self.noise_std == 0:
-                self.__dict__["_pop_cache"] = (vals, (float(self.min_fr), float(self.max_fr)), pop)
-        if self.noise_std != 0:  # the OU parameters of update() (Neurons.py:153-168) at the agent's dt
+        return pop
+
+    def _population_noise(self, pop):
+        """... and, last, the OU parameters of update() (Neurons.py:153-168) at the agent's dt."""
+        if self.noise_std != 0:
             pop.noise_state = self._noise.data_ptr()
             pop.noise_theta_dt, pop.noise_sigma_dt = self._noise_constants(self.Agent.dt)
         return pop
@@ -226,7 +213,7 @@ class Neurons:
         Ag = self.Agent
         st = Ag._plan
         if st is not None:
-            if not kwargs and st.__class__.__name__ == "AutoStepper" and st.step_population(self):
+            if not kwargs and st.serves_updates and st.step_population(self):
                 return  # served from the native plan of the unchanged per-step loop (plan.AutoStepper)
             st.close()  # eager stepping resumes: the plan's open rows and cursors would go stale
         u = kwargs.pop("spike_uniforms", None)
@@ -1522,6 +1509,30 @@ class FeedForwardLayer(Neurons):
             d.update(spec)
             p = (d["gain"], d["threshold"], 0, 0)
         return _L.ACTIVATIONS[name], (_L.C.c_float * 4)(*[float(x) for x in p])
+
+    def _population(self, plan_index=None):
+        """The layer as a step plan's RiabPopulation: its inputs are populations recorded in the plan before it."""
+        entries = list(self.inputs.values())
+        if len(entries) > 8:
+            raise ValueError("a FeedForwardLayer in a step plan takes at most 8 input layers")
+        pop = self._population_header()
+        pop.kind, pop.n_inputs = _L.POP_KINDS["ff"], len(entries)
+        keep = []
+        for l, e in enumerate(entries):
+            if plan_index is None or e["layer"] not in plan_index:
+                raise NotImplementedError(f"input layer {e['layer'].name} must be recorded in the plan before "
+                                          f"{self.name} (recurrent inputs advance through update())")
+            wt = self._device_weights(e)
+            pop.input_index[l], pop.input_wt[l] = plan_index[e["layer"]], wt.data_ptr()
+            keep.append(wt)
+        bias = np.asarray(self.biases, dtype=np.float32).reshape(-1)
+        bias_t = self._tables((bias,), lambda: torch.from_numpy(bias.copy()).to(self._device))
+        act, pars = self._activation()
+        pop.bias, pop.activation, pop.rates_prime = bias_t.data_ptr(), act, self._rates_prime.data_ptr()
+        for i in range(4):
+            pop.act_params[i] = pars[i]
+        self._plan_tables = keep + [bias_t]
+        return self._population_noise(pop)
 
     def _auto_key(self):
         acts = self._activation()

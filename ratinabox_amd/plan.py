@@ -12,7 +12,19 @@ path uses; the Python mirrors (`history`, `firingrate`, `_times`) are brought up
 kernels, same arguments, same RNG counters.  Populations with `noise_std > 0` are covered (their OU
 parameters follow the dt of the step, as update() reads Agent.dt), FeedForwardLayers too as long as
 their input layers are recorded before them (weights are read from the device copies made when the plan is built:
-rebuild the plan after editing `inputs[...]["w"]`)."""
+rebuild the plan after editing `inputs[...]["w"]`).
+
+Who owns what:
+  `_NativePlan`  the `riab_plan_*` handle and everything that runs once per plan, attach, sync or close: recording the
+                 agent and its populations, opening history rows (`_open_agent_rows`, `_open_pop_rows`: the scratch row
+                 of a population without history included), publishing them (`_publish_agent`, `_publish_pop`),
+                 `close()` / `settle()` / `info()`, and `serves_updates` / `discard_ahead()`, which callers ask instead
+                 of the class.
+  `StepPlan`     `step()`, `attach_task()`; ONE pending counter and clock list, so every history opens the same
+                 number of rows (`_attach`) and is re-opened before the call that would not fit.
+  `AutoStepper`  `step_agent()` / `step_population()` behind the unchanged `Ag.update(); N.update()` loop; pending
+                 counters per owner, rows re-opened per owner after RIAB_EFULL, the staleness keys, the back-off when
+                 it closes."""
 import numpy as np
 import torch
 
@@ -98,7 +110,7 @@ def _settle_fused(plan):
                 kp = None if t_s is None else next((j for j in range(len(N._times) - 1, max(-1, len(N._times) - 3 - back), -1)
                                                     if N._times[j] == t_s), None)
                 if kp is None:
-                    if back == 0 and hasattr(plan, "discard_ahead"):
+                    if back == 0:
                         plan.discard_ahead()   # (written ahead, its update() not called yet: that call recomputes it)
                     continue
                 fr = N._hist_fr.row(kp)
@@ -168,55 +180,159 @@ class _ForcedRows:
         self.left -= n
 
 
-class StepPlan:
-    def __init__(self, agent, neurons=None, capacity=1024):
+class _NativePlan:
+    """One `riab_plan_*` handle and what both ways of driving it share: recording the agent and its populations,
+    handing history rows to the plan, publishing the rows it wrote, closing.  Everything here runs once per plan, attach,
+    sync or close; the per-step paths are the subclasses' own."""
+
+    serves_updates = False    # True: Agent.update() / Neurons.update() are served from this plan (AutoStepper)
+
+    def __init__(self, agent, neurons, forced_block=None):
         self.agent = agent
-        self.neurons = list(agent.Neurons if neurons is None else neurons)
-        self.capacity = int(capacity)
+        self.neurons = list(neurons)
         agent._sync_plan()
         if agent._plan is not None:
             agent._plan.close()
         Bp = agent._Bp
         self._row_scratch = torch.empty((_L.HIST_ROWS, Bp), dtype=torch.float32, device=agent._device)
         self._dt = agent.dt      # the dt the noisy populations' OU constants in the plan were computed for
-        self._drift_key = None
-        self._drift_t = None
-        env, self._walls = agent.Environment.device_tables(agent._device)
-        motion = agent._motion(agent.dt, False, 1, {})
-        self._h = _L.lib.riab_plan_create(env, motion, _L.ptr(agent._state), Bp, int(agent.agent_id0), int(agent.rng_seed),
-                                          int(agent._step_index), _L.ptr(self._row_scratch),
-                                          _L.ptr(agent._diag))
-        if not self._h:
+        self._env_struct, self._walls = agent.Environment.device_tables(agent._device)
+        self._motion = agent._motion(agent.dt, False, 1, {})
+        h = _L.lib.riab_plan_create(self._env_struct, self._motion, _L.ptr(agent._state), Bp, int(agent.agent_id0),
+                                    int(agent.rng_seed), int(agent._step_index), _L.ptr(self._row_scratch),
+                                    _L.ptr(agent._diag))
+        if not h:
             raise _L.RiabError("riab_plan_create failed")
+        self._h = _L.C.c_void_p(h)
         _L.check(_L.lib.riab_plan_set_clock(self._h, float(agent.t)), "riab_plan_set_clock")   # (Agent.t: the theta phase)
-        self._forced = _ForcedRows(agent, self._h, block=self.capacity) if agent.use_imported_trajectory else None
-        self._step_fn = _L.lib.riab_plan_step
+        self._forced = _ForcedRows(agent, self._h, block=forced_block) if agent.use_imported_trajectory else None
+        # (a step is a few us of GPU time: the stream handle comes straight from the C API by the agent's device index,
+        # the subclasses bind their entry points once)
         raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
         self._raw_stream = raw if raw is not None else (lambda _i: torch.cuda.current_stream().cuda_stream)
         self._dev_index = agent._device_index
-        self._pops = []
-        index = {}
+        self._index, self._pops = {}, []     # {population: its index in the plan}; the descriptors, kept alive
         for N in self.neurons:
-            pop = N._population(index)
+            pop = N._population(self._index)          # (raises NotImplementedError for populations a plan cannot hold)
             N._plan_scratch(pop)
-            index[N] = len(index)
             idx = _L.lib.riab_plan_add(self._h, pop)
             if idx < 0:
                 raise _L.RiabError(f"riab_plan_add failed: {_L.strerror(idx)}")
+            self._index[N] = idx
             self._pops.append(pop)
         _attach_fused(self, agent)
+        self._agent_rows = None
+        self._pop_rows = [None] * len(self.neurons)
+        self._scratch_rates = [None] * len(self.neurons)
+        agent._plan = self
+
+    # ---- history rows: opened (not yet history), handed to the plan ---------------------------------
+    def _open_agent_rows(self, cap, full=None):
+        """Up to `cap` free rows of the agent's history (a new chunk has `full` rows) go to the plan; the rows opened."""
+        ag = self.agent
+        self._agent_rows = ag._hist.open_rows(cap, full) if ag.save_history else None
+        rows = 0 if self._agent_rows is None else int(self._agent_rows.shape[0])
+        _L.check(_L.lib.riab_plan_set_agent_history(self._h, _L.ptr(self._agent_rows), rows), "riab_plan_set_agent_history")
+        return rows
+
+    def _open_pop_rows(self, i, cap, full=None):
+        """The same for population i: rates and spikes advance together.  Without a history: one persistent scratch row."""
+        N = self.neurons[i]
+        if N.save_history:
+            fr = N._hist_fr.open_rows(cap, full)
+            rows = int(fr.shape[0])
+            sp = N._hist_sp.open_rows(rows, full) if N.save_spikes else None
+        else:
+            if self._scratch_rates[i] is None:
+                ag = self.agent
+                self._scratch_rates[i] = torch.empty((1, int(N.n), ag._Bp), dtype=torch.float32, device=ag._device)
+            fr, sp, rows = self._scratch_rates[i], None, 0
+        self._pop_rows[i] = (fr, sp)
+        _L.check(_L.lib.riab_plan_set_population_history(self._h, i, _L.ptr(fr), _L.ptr(sp), rows),
+                 "riab_plan_set_population_history")
+        return rows
+
+    # ---- publishing: the first n of the opened rows, `done` of which were published before, become history ---------
+    def _publish_agent(self, n, times, done):
+        ag = self.agent
+        if ag.save_history:
+            ag._hist.commit(n)
+            ag._times.extend(times)
+            ag._last_row = self._agent_rows[done + n - 1]
+        else:
+            ag._last_row = self._row_scratch
+        return done + n
+
+    def _publish_pop(self, i, n, times, done):
+        N = self.neurons[i]
+        fr, sp = self._pop_rows[i]
+        if N.save_history:
+            N._hist_fr.commit(n)
+            if sp is not None:
+                N._hist_sp.commit(n)
+            N._times.extend(times)
+            N._rates = fr[done + n - 1]
+            N._spikes_last = None if sp is None else sp[done + n - 1]
+        else:
+            N._rates = fr[0]
+        return done + n
+
+    def discard_ahead(self):
+        """Rows written ahead of their population's update() are stale: only a plan that serves update() has any."""
+
+    def _closing(self):
+        """close(): the plan is off its agent, its handle still alive."""
+
+    def close(self):
+        """Detach from the agent (called automatically when the agent is stepped eagerly)."""
+        self.sync()
+        if self.agent._plan is self:
+            self.agent._plan = None
+        self._closing()
+        if self._h:
+            try:
+                _settle_fused(self)
+            finally:
+                self._destroy()
+
+    def _destroy(self):
+        if getattr(self, "_h", None):
+            _L.lib.riab_plan_destroy(self._h)
+            self._h = None
+
+    def settle(self):
+        """Look at the one-launch step's give-up counter; recover (see _settle_fused)."""
+        _settle_fused(self)
+
+    def info(self):
+        """Launch accounting of the native plan (riab_plan_info)."""
+        return _plan_info(self._h)
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:  # noqa: BLE001 (interpreter shutdown)
+            pass
+
+
+class StepPlan(_NativePlan):
+    """`plan.step(n)`: n steps of the agent and every recorded population in one native call.  ONE pending counter and
+    ONE list of clocks for all histories, which therefore open the same number of rows."""
+
+    def __init__(self, agent, neurons=None, capacity=1024):
+        self.capacity = int(capacity)
+        super().__init__(agent, agent.Neurons if neurons is None else neurons, forced_block=self.capacity)
+        self._drift_key = None
+        self._drift_t = None
+        self._step_fn = _L.lib.riab_plan_step
         self._pending = 0        # steps taken since the last sync()
         self._times_pending = []
         self._rows_open = 0      # rows still free in the attached chunks
         self._chunk_rows_done = 0
-        self._agent_rows = None
-        self._pop_rows = [None] * len(self.neurons)
-        self._scratch_rates = [None] * len(self.neurons)
         self._task_env = None    # TaskEnvironment attached by attach_task()
         self._actions = None     # persistent drift buffer [2, Bp] the plan reads when a task is attached
         self._auto_reset = False
         self._scripted = False
-        agent._plan = self
         self._attach()
 
     # ---- history chunks --------------------------------------------------------------------------
@@ -234,24 +350,9 @@ class StepPlan:
                 h.preallocate(cap)
             if h.free_rows() > 0:
                 cap = min(cap, h.free_rows())
-        if ag.save_history:
-            self._agent_rows = ag._hist.open_rows(cap, self.capacity)
-            _L.check(_L.lib.riab_plan_set_agent_history(self._h, _L.ptr(self._agent_rows), cap), "riab_plan_set_agent_history")
-        else:
-            self._agent_rows = None
-            _L.check(_L.lib.riab_plan_set_agent_history(self._h, None, 0), "riab_plan_set_agent_history")
-        for i, N in enumerate(self.neurons):
-            if N.save_history:
-                fr = N._hist_fr.open_rows(cap, self.capacity)
-                sp = N._hist_sp.open_rows(cap, self.capacity) if N.save_spikes else None
-                self._pop_rows[i] = (fr, sp)
-                rc = _L.lib.riab_plan_set_population_history(self._h, i, _L.ptr(fr), _L.ptr(sp), cap)
-            else:
-                if self._scratch_rates[i] is None:
-                    self._scratch_rates[i] = torch.empty((1, int(N.n), ag._Bp), dtype=torch.float32, device=ag._device)
-                self._pop_rows[i] = (self._scratch_rates[i], None)
-                rc = _L.lib.riab_plan_set_population_history(self._h, i, _L.ptr(self._scratch_rates[i]), None, 0)
-            _L.check(rc, "riab_plan_set_population_history")
+        self._open_agent_rows(cap, self.capacity)
+        for i in range(len(self.neurons)):
+            self._open_pop_rows(i, cap, self.capacity)
         self._rows_open = cap
         self._chunk_rows_done = 0
 
@@ -361,57 +462,15 @@ class StepPlan:
         if not n:
             return
         self._pending = 0
-        ag = self.agent
         times, self._times_pending = self._times_pending, []
         done = self._chunk_rows_done
-        if ag.save_history:
-            ag._hist.commit(n)
-            ag._times.extend(times)
-            ag._last_row = self._agent_rows[done + n - 1]
-        else:
-            ag._last_row = self._row_scratch
-        for N, (fr, sp) in zip(self.neurons, self._pop_rows):
-            if N.save_history:
-                N._hist_fr.commit(n)
-                if sp is not None:
-                    N._hist_sp.commit(n)
-                N._times.extend(times)
-                N._rates = fr[done + n - 1]
-                N._spikes_last = None if sp is None else sp[done + n - 1]
-            else:
-                N._rates = fr[0]
+        self._publish_agent(n, times, done)
+        for i in range(len(self.neurons)):
+            self._publish_pop(i, n, times, done)
         self._chunk_rows_done = done + n
 
-    def close(self):
-        """Detach from the agent (called automatically when the agent is stepped eagerly)."""
-        self.sync()
-        if self.agent._plan is self:
-            self.agent._plan = None
-        if self._h:
-            try:
-                _settle_fused(self)
-            finally:
-                _L.lib.riab_plan_destroy(self._h)
-                self._h = None
 
-    def settle(self):
-        """Look at the one-launch step's give-up counter; recover (see _settle_fused)."""
-        _settle_fused(self)
-
-    def info(self):
-        """Launch accounting of the native plan (riab_plan_info)."""
-        return _plan_info(self._h)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _L.lib.riab_plan_destroy(self._h)
-                self._h = None
-        except Exception:  # noqa: BLE001 (interpreter shutdown)
-            pass
-
-
-class AutoStepper:
+class AutoStepper(_NativePlan):
     """The reference's per-object loop served natively WITHOUT the caller changing a line:
 
         for i in range(T):
@@ -437,94 +496,41 @@ class AutoStepper:
     CAPACITY = 4096          # rows per attached history chunk, at most
     CHUNK_BYTES = 4 << 30    # ... and at most this much HBM per population and chunk (cfg 2: 16.8 MB per row -> 255 rows)
 
+    serves_updates = True
+
     def __init__(self, agent):
-        self.agent = agent
-        self.neurons = list(agent.Neurons)
-        agent._sync_plan()
-        if agent._plan is not None:
-            agent._plan.close()
-        Bp = agent._Bp
-        self._row_scratch = torch.empty((_L.HIST_ROWS, Bp), dtype=torch.float32, device=agent._device)
-        self._dt = agent.dt
-        self._env_struct, self._walls = agent.Environment.device_tables(agent._device)
-        self._motion = agent._motion(agent.dt, False, 1, {})
-        self._motion_key = agent._motion_cache[0]
+        super().__init__(agent, agent.Neurons)
+        self._motion_key = agent._motion_key_now(agent.dt)   # (what the recorded motion struct was resolved from)
         self._drift_buf = None
-        self._h = _L.lib.riab_plan_create(self._env_struct, self._motion, _L.ptr(agent._state), Bp, int(agent.agent_id0),
-                                          int(agent.rng_seed), int(agent._step_index),
-                                          _L.ptr(self._row_scratch), _L.ptr(agent._diag))
-        if not self._h:
-            raise _L.RiabError("riab_plan_create failed")
-        self._h = _L.C.c_void_p(self._h)
-        _L.check(_L.lib.riab_plan_set_clock(self._h, float(agent.t)), "riab_plan_set_clock")
-        self._forced = _ForcedRows(agent, self._h) if agent.use_imported_trajectory else None
         self._traj_id = getattr(agent, "_trajectory_id", 0)
-        self._index, self._pops, self._keys = {}, [], []
-        for N in self.neurons:
-            pop = N._population(self._index)          # (raises NotImplementedError for populations a plan cannot hold)
-            N._plan_scratch(pop)
-            idx = _L.lib.riab_plan_add(self._h, pop)
-            if idx < 0:
-                raise _L.RiabError(f"riab_plan_add failed: {_L.strerror(idx)}")
-            self._index[N] = idx
-            self._pops.append(pop)
-            self._keys.append(N._auto_key())
-        _attach_fused(self, agent)
-        # (two native calls per step of the user's loop: the stream handle straight from the C API by device index, the
-        # entry points bound once)
-        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        self._raw_stream = raw if raw is not None else (lambda _i: torch.cuda.current_stream().cuda_stream)
-        self._dev_index = agent._device_index
+        # (two native calls per step of the user's loop, the entry points bound once)
         self._step_agent_fn, self._step_pop_fn = _L.lib.riab_plan_step_agent, _L.lib.riab_plan_step_population
-        self._a_pending, self._a_times = 0, []
+        self._served = 0         # Agent.update() calls served: close() backs off when they were few
+        # (pending rows, their clocks and the rows published of what is open: one each for the agent and every population)
+        self._a_pending, self._a_times, self._a_done = 0, [], 0
         self._p_pending = [0] * len(self.neurons)
         self._p_times = [[] for _ in self.neurons]
-        self._agent_rows, self._a_done = None, 0
-        self._pop_rows = [None] * len(self.neurons)
         self._p_done = [0] * len(self.neurons)
-        self._scratch_rates = [None] * len(self.neurons)
-        agent._plan = self
-        self._attach()
-
-    # ---- history chunks -------------------------------------------------------------------------
-    def _attach(self):
+        self._keys = [N._auto_key() for N in self.neurons]    # what each population's update() depends on, by value
         self._attach_agent()
         for i in range(len(self.neurons)):
             self._attach_pop(i)
 
+    # ---- history chunks -------------------------------------------------------------------------
     def _attach_agent(self):
         """Open history rows for the agent (what is left of the current chunk, else a new chunk) — the agent's only:
         a full agent chunk does not touch the populations' part-filled ones."""
         self.sync()
-        ag = self.agent
-        if ag.save_history:
-            self._agent_rows = ag._hist.open_rows(self.CAPACITY)
-            rc = _L.lib.riab_plan_set_agent_history(self._h, _L.ptr(self._agent_rows), int(self._agent_rows.shape[0]))
-        else:
-            self._agent_rows = None
-            rc = _L.lib.riab_plan_set_agent_history(self._h, None, 0)
-        _L.check(rc, "riab_plan_set_agent_history")
+        self._open_agent_rows(self.CAPACITY)
         self._a_done = 0
 
     def _attach_pop(self, i):
-        N, ag = self.neurons[i], self.agent
+        N = self.neurons[i]
         self._sync_pop(i)
-        if N.save_history:
-            full = cap = int(max(64, min(self.CAPACITY, self.CHUNK_BYTES // max(1, int(N.n) * ag._Bp * 4))))
-            if N.save_spikes:  # (rates and spikes advance together; should their free tails differ, the shorter one counts)
-                tails = [h.free_rows() for h in (N._hist_fr, N._hist_sp) if h.free_rows() > 0]
-                cap = min([cap] + tails)
-            fr = N._hist_fr.open_rows(cap, full)   # (a history without free rows opens a full-sized chunk, not a `cap`-row one)
-            cap = int(fr.shape[0])
-            sp = N._hist_sp.open_rows(cap, full) if N.save_spikes else None
-            self._pop_rows[i] = (fr, sp)
-            rc = _L.lib.riab_plan_set_population_history(self._h, i, _L.ptr(fr), _L.ptr(sp), cap)
-        else:
-            if self._scratch_rates[i] is None:
-                self._scratch_rates[i] = torch.empty((1, int(N.n), ag._Bp), dtype=torch.float32, device=ag._device)
-            self._pop_rows[i] = (self._scratch_rates[i], None)
-            rc = _L.lib.riab_plan_set_population_history(self._h, i, _L.ptr(self._scratch_rates[i]), None, 0)
-        _L.check(rc, "riab_plan_set_population_history")
+        full = cap = int(max(64, min(self.CAPACITY, self.CHUNK_BYTES // max(1, int(N.n) * self.agent._Bp * 4))))
+        if N.save_history and N.save_spikes:  # (should the free tails of rates and spikes differ, the shorter one counts)
+            cap = min([cap] + [h.free_rows() for h in (N._hist_fr, N._hist_sp) if h.free_rows() > 0])
+        self._open_pop_rows(i, cap, full)     # (a history without free rows opens a full-sized chunk, not a `cap`-row one)
         self._p_done[i] = 0
 
     # ---- the two fast paths ---------------------------------------------------------------------
@@ -568,7 +574,7 @@ class AutoStepper:
         ag._step_index += 1
         self._a_pending += 1
         self._a_times.append(ag.t)
-        self._served = getattr(self, "_served", 0) + 1
+        self._served += 1
         return True
 
     def _write_drift(self, x):
@@ -612,70 +618,26 @@ class AutoStepper:
     # ---- publishing -----------------------------------------------------------------------------
     def _sync_pop(self, i):
         n = self._p_pending[i]
-        if not n or self._pop_rows[i] is None:
-            return
-        self._p_pending[i] = 0
-        N = self.neurons[i]
-        fr, sp = self._pop_rows[i]
-        times, self._p_times[i] = self._p_times[i], []
-        if N.save_history:
-            done = self._p_done[i]
-            N._hist_fr.commit(n)
-            if sp is not None:
-                N._hist_sp.commit(n)
-            N._times.extend(times)
-            N._rates = fr[done + n - 1]
-            N._spikes_last = None if sp is None else sp[done + n - 1]
-            self._p_done[i] = done + n
-        else:
-            N._rates = fr[0]
+        if n and self._pop_rows[i] is not None:
+            self._p_pending[i] = 0
+            times, self._p_times[i] = self._p_times[i], []
+            self._p_done[i] = self._publish_pop(i, n, times, self._p_done[i])
 
     def sync(self):
         """Publish the rows written since the last sync to the Python-side mirrors."""
-        ag = self.agent
         n = self._a_pending
         if n:
             self._a_pending = 0
             times, self._a_times = self._a_times, []
-            if ag.save_history:
-                ag._hist.commit(n)
-                ag._times.extend(times)
-                ag._last_row = self._agent_rows[self._a_done + n - 1]
-                self._a_done += n
-            else:
-                ag._last_row = self._row_scratch
+            self._a_done = self._publish_agent(n, times, self._a_done)
         for i in range(len(self.neurons)):
             self._sync_pop(i)
 
-    def close(self):
-        self.sync()
+    def _closing(self):
+        """Back-off: a stepper that was closed after a handful of steps was not worth recording."""
         ag = self.agent
-        if ag._plan is self:
-            ag._plan = None
         ag._auto_streak = 0
-        # back-off: a stepper that was closed after a handful of steps was not worth recording
-        served = getattr(self, "_served", 0)
-        if served < ag.AUTO_KEEP:
+        if self._served < ag.AUTO_KEEP:
             ag._auto_after = min(2 * max(ag._auto_after, 1), ag.AUTO_AFTER_MAX)
         else:
             ag._auto_after = ag.AUTO_AFTER
-        if self._h:
-            try:
-                _settle_fused(self)
-            finally:
-                _L.lib.riab_plan_destroy(self._h)
-                self._h = None
-
-    def settle(self):
-        _settle_fused(self)
-
-    def info(self):
-        return _plan_info(self._h)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _L.lib.riab_plan_destroy(self._h)
-                self._h = None
-        except Exception:  # noqa: BLE001 (interpreter shutdown)
-            pass

@@ -963,8 +963,56 @@ def test_unchanged_reference_loop_is_served_natively_and_bit_identical(riab, scr
             np.testing.assert_array_equal(a[k], b[k], err_msg=k)
 
 
+def _rollover_loop(riab, auto):
+    """150 rounds of the unchanged loop in a 256-agent world (the one-launch step is attached): a population with spikes,
+    one without, one without history."""
+    os.environ["RIAB_NO_AUTO_PLAN"] = "0" if auto else "1"
+    try:
+        np.random.seed(11)
+        ag = riab.Agent(riab.Environment({}), {"n_agents": 256, "dt": 0.02, "seed": 4})
+        np.random.seed(12)
+        pops = [riab.PlaceCells(ag, {"n": 16}), riab.GridCells(ag, {"n": 8, "save_spikes": False}),
+                riab.HeadDirectionCells(ag, {"n": 4, "save_history": False})]
+        engaged = []
+        for _ in range(150):
+            ag.update()
+            for p in pops:
+                p.update()
+            engaged.append(ag._plan is not None and type(ag._plan).__name__ == "AutoStepper")
+        torch.cuda.synchronize()
+        if auto:   # (the rows open at the end: the agent's window is CAPACITY rows, a population's its 64-row floor)
+            assert ag._plan._agent_rows.shape[0] == 6 and ag._plan._pop_rows[0][0].shape[0] == 64
+        out = {"traj": ag.get_history_tensor().cpu().numpy(), "state": ag.state_tensor.cpu().numpy(), "t": list(ag.history["t"])}
+        for i, p in enumerate(pops):
+            fr, sp = p.get_history_tensors()
+            out[f"fr{i}"], out[f"sp{i}"], out[f"t{i}"] = fr.cpu().numpy(), sp.cpu().numpy(), list(p.history["t"])
+            out[f"last{i}"] = p.firingrate
+        return out, engaged
+    finally:
+        os.environ.pop("RIAB_NO_AUTO_PLAN", None)
+
+
+def test_auto_stepper_rollover_bit_identical_to_eager(riab, monkeypatch):
+    """The stepper's rows run out and are opened anew — the agent's every 6 steps (CAPACITY = 6), a population's every
+    64 (its floor), each owner on its own RIAB_EFULL — and the 150 rounds give, bit for bit, what the eager calls give:
+    state, agent history, every rate and spike history, times, firingrate."""
+    from ratinabox_amd.plan import AutoStepper
+    monkeypatch.setattr(AutoStepper, "CAPACITY", 6)
+    a, engaged = _rollover_loop(riab, True)
+    b, engaged_b = _rollover_loop(riab, False)
+    assert all(engaged[8:]) and not any(engaged_b)
+    assert a["traj"].shape[0] == 150 and a["fr0"].shape[0] == 150 and a["sp0"].shape[0] == 150 and a["fr1"].shape[0] == 150
+    assert a["sp1"].shape[0] == 0 and a["fr2"].shape[0] == 0 and len(a["t"]) == 150
+    assert a.keys() == b.keys()
+    for k in a:
+        if isinstance(a[k], list):
+            assert a[k] == b[k], k
+        else:
+            np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
 # ----------------------------------------------------------------------------- several populations, one native call
-L_ROOM = [[0, 0], [1, 0], [1, 0.5], [0.5, 0.5], [0.5, 1], [0, 1]]
+L_ROOM =[[0, 0], [1, 0], [1, 0.5], [0.5, 0.5], [0.5, 1], [0, 1]]
 
 
 def _multi_world(riab, B, seed=5, polygon=False):
