@@ -738,7 +738,14 @@ int riab_task_world_goal_vector(const RiabEnv* env, const RiabTask* task, double
  * Agent.update, clock += dt_env, riab_task_step, [auto_reset: riab_task_reset(mask = terminal_out) with
  * the reset counter advanced every step], then the populations (which therefore see teleported
  * positions).  Task arrays hold task_B lanes (the agents of the batch, without the padding of the
- * plan's B).  task == NULL detaches. */
+ * plan's B).  task == NULL detaches.
+ * A plan that holds a learner (riab_plan_set_learner) LEARNS, THEN RESETS — the step's order is
+ *   [scripted action], Agent.update, clock += dt_env, riab_task_step, every population in list order (a learner's
+ *   forward pass included), riab_td_learn_step of every learner with [auto_reset: mask = terminal_out],
+ *   [auto_reset: riab_task_reset(mask = terminal_out), the reset counter advanced every step]
+ * so the value of the state that earned the reward is learned before the lane is teleported, the populations see the
+ * positions BEFORE the teleport, the task's reset still patches the newest history row, and the coming step's scripted
+ * action is worked out after the reset.  Such a plan never takes the one-launch task step. */
 int riab_plan_set_task(RiabPlan* plan, const RiabTask* task, double* task_state, int64_t task_B, double t_env,
                        double dt_env, double* reward_out, uint8_t* terminal_out, int32_t* task_diag,
                        int32_t auto_reset, int32_t n_select, int32_t ordered, uint64_t task_seed,
@@ -751,6 +758,7 @@ double riab_plan_task_clock(const RiabPlan* plan);
  * [auto_reset: riab_task_world_reset(only_if_terminal = 1, with the next step's scripted action), the reset counter
  * advanced every step], then the populations.  world == NULL: back to per-lane. */
 int riab_plan_set_task_world(RiabPlan* plan, double* world, uint64_t* met_scratch, int32_t* cand_scratch, int32_t* ctl);
+/* (riab_plan_set_learner: with the riab_td_* entry points below) */
 
 /* ---- the open-loop path as ONE native call: flag-coupled trajectory + firing-rate kernels -------
  * `for t in range(T): Agent.update(); [N.update() for N in Neurons]` (demos/simple_example.ipynb cell 4;
@@ -1049,6 +1057,43 @@ int riab_td_update(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_l
  * td: at most 8). */
 int riab_td_reset(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers, float* const* rows,
                   int32_t n_rows, const uint8_t* mask, riab_stream_t stream);
+
+/* `ValueNeuron.learn(reward); ValueNeuron.reset(lanes = mask)` behind the forward pass, in TWO launches: what
+ * riab_td_forward_tail(with_trace = 0) + riab_td_update(fuse_trace = 1) + riab_td_reset(mask) do in four, with the same
+ * bits in the weights, the traces, v_last, dvdt and td.  The gradient launch works dvdt = (v - v_last) / dt out on the
+ * fly and stores it with td (more than 256 neurons: the stand-alone trace launch goes first, as in riab_td_update); the
+ * finish launch adds the partial sums in riab_td_update's order, copies v to v_last and zeroes the columns b < B with
+ * mask[b] != 0 of the traces, v_last, dvdt, td and — zero_v != 0 only: a caller whose v is a row of a history passes 0 and
+ * keeps what was recorded — of v.  mask: device uint8 [B], or NULL (nothing is reset).  Other arguments as riab_td_update. */
+int riab_td_learn_step(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers, const void* reward,
+                       int32_t reward_f64, int64_t reward_ld_n, int64_t reward_ld_b, float* v, float* v_last, float* dvdt,
+                       const float* prime, float* td, const uint8_t* mask, int32_t zero_v, float* workspace,
+                       int64_t workspace_floats, riab_stream_t stream);
+
+/* Make the feed-forward population `index` of the plan a TD learner (contribs.ValueNeuron / SuccessorFeatures): after the
+ * populations of a step riab_plan_step runs riab_td_learn_step on it — v its row of the step, the layers its inputs'
+ * rows, weights its input_wt (the buffers its forward pass reads), prime its rates_prime — and then the deferred resets
+ * (riab_plan_set_task).  p: the learner's constants (p->n the population's n, p->Bp the plan's B); traces: one device
+ * float32 [n_in][Bp] per input, in input order; v_last, dvdt, td device float32 [n][Bp]; workspace: riab_td_workspace()
+ * floats.  Where the reward comes from: */
+enum {
+  RIAB_REWARD_NONE = 0,       /* not bound yet: riab_plan_step returns RIAB_EINVAL before anything is launched */
+  RIAB_REWARD_TASK = 1,       /* the attached task's reward_out (float64 [B], strides 0, 1); no task at the step: RIAB_EINVAL */
+  RIAB_REWARD_POINTER = 2,    /* `reward` (reward_f64, reward_ld_n, reward_ld_b as riab_td_update), read in place every step */
+  RIAB_REWARD_POPULATION = 3  /* this step's row of population reward_index (SuccessorFeatures' features), one of the
+                                 populations ahead of the learner with the learner's n */
+};
+/* Checked here, before anything is launched: RIAB_EINVAL for an index that is no feed-forward population, a reward_index
+ * that is not smaller than `index`, an n other than the reward population's or the population's own, a Bp other than the
+ * plan's B, a workspace that is too short; RIAB_EALIGN for a pointer that is not 16-byte aligned (the reward: its element
+ * size); RIAB_ETOOBIG as riab_td_update.  Calling it again for the same index replaces the record (a new reward source).
+ * riab_plan_step_agent and riab_plan_step_population return RIAB_EUNSUPPORTED on a plan with a learner; a learner without
+ * a history chunk whose row another learner reads (as an input or as its reward) is refused by riab_plan_step with
+ * RIAB_EUNSUPPORTED: its reset would zero the row before the other has learned from it. */
+int riab_plan_set_learner(RiabPlan* plan, int32_t index, const RiabTDParams* p, float* const* traces, float* v_last,
+                          float* dvdt, float* td, float* workspace, int64_t workspace_floats, int32_t reward_kind,
+                          const void* reward, int32_t reward_f64, int64_t reward_ld_n, int64_t reward_ld_b,
+                          int32_t reward_index);
 
 /* ---- contribs.SubAgent: theta sequences (reference contribs/SubAgent.py) -----------------------------------------
  * A SubAgent is an Agent whose position is a function of another Agent's (the lead's) state.  The entry points below

@@ -1173,7 +1173,9 @@ class Agent:
 
     def make_step_plan(self, neurons=None, capacity=1024):
         """A `StepPlan` (plan.py): `plan.step()` == `Agent.update(); N.update() for N in neurons` with the
-        per-step host work done in one native call."""
+        per-step host work done in one native call.  A learning contribs.ValueNeuron / SuccessorFeatures among the
+        neurons learns inside the plan: after the populations, every step runs its `learn(reward)` — the reward bound with
+        `plan.bind_reward(VN, tensor)`, the features' row for SuccessorFeatures (plan.py: "learn, then reset")."""
         from .plan import StepPlan
         return StepPlan(self, neurons, capacity)
 

@@ -162,6 +162,8 @@ def ctrl_words(B):
     """RIAB_CTRL_WORDS(B): control words of the flag-coupled pipeline for B agents."""
     return CTRL_PROGRESS + 32 * ((int(B) + 255) // 256)
 
+REWARD_NONE, REWARD_TASK, REWARD_POINTER, REWARD_POPULATION = range(4)    # riab_hip.h RIAB_REWARD_*
+
 ACTIVATIONS = {"linear": 0, "sigmoid": 1, "relu": 2, "tanh": 3, "retanh": 4, "softmax": 5}
 
 # name -> (restype, argtypes): every symbol include/riab_hip.h declares
@@ -211,6 +213,12 @@ PROTOTYPES = {
     "riab_td_update": (C.c_int, [C.POINTER(RiabTDParams), C.POINTER(RiabTDLayer), C.c_int32, C.c_void_p, C.c_int32,
                                  C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    "riab_td_learn_step": (C.c_int, [C.POINTER(RiabTDParams), C.POINTER(RiabTDLayer), C.c_int32, C.c_void_p, C.c_int32,
+                                     C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "riab_plan_set_learner": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(RiabTDParams), C.POINTER(C.c_void_p), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_int64, C.c_int64, C.c_int32]),
     "riab_td_reset": (C.c_int, [C.POINTER(RiabTDParams), C.POINTER(RiabTDLayer), C.c_int32, C.POINTER(C.c_void_p),
                                 C.c_int32, C.c_void_p, C.c_void_p]),
     "riab_theta_sequence_step": (C.c_int, [C.POINTER(RiabEnv), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,

@@ -3,9 +3,11 @@ ratinabox/contribs/SuccessorFeatures.py): a `ValueNeuron` with one value neuron 
 features' firing rate.  `params["features"]` is any population of the same Agent; `params["input_layers"]` are the basis
 features the successor features are a weighted sum of.  `update_weights()` hands the features' device-resident last
 rates `[n][B_padded]` to the TD kernel as they are: one reward per (neuron, agent), no copy.  Like the reference,
-`update()` does not update the features or the basis features: the loop does."""
+`update()` does not update the features or the basis features: the loop does.  In a `StepPlan` the reward is this step's
+row of the features, which must be recorded in the plan before the learner."""
 import copy
 
+from .. import _lib as _L
 from .ValueNeuron import ValueNeuron
 
 
@@ -30,3 +32,9 @@ class SuccessorFeatures(ValueNeuron):
     def learn(self, **kwargs):
         """`update(); update_weights()` with the trace update riding in the gradient kernel (ValueNeuron.learn)."""
         super().learn(self.params["features"]._rates, **kwargs)
+
+    def _plan_reward(self, plan_index):
+        feats = self.params["features"]
+        if feats not in plan_index:
+            raise NotImplementedError(f"the features {feats.name} must be recorded in the plan before {self.name}")
+        return _L.REWARD_POPULATION, plan_index[feats]

@@ -535,7 +535,13 @@ class TaskEnvironment(Environment):
         writer workgroups keep the world's books, the one that takes the last ticket walks the shared list, resets the world
         when its episode ended and posts the verdict; the store-bound populations ride along); other batches take three
         launches inside the one native call: motion + the world's step, its reset when the episode ended (decided on the
-        device) + the next scripted action, the populations."""
+        device) + the next scripted action, the populations.
+
+        With a learning contribs.ValueNeuron / SuccessorFeatures among the neurons the step LEARNS, THEN RESETS:
+        `env.step`, every population's `update()`, `VN.learn(env.get_reward())`, and only then — with `auto_reset` —
+        `VN.reset(lanes=terminal)` and `env.reset(mask=terminal)`: the populations see the positions before the teleport,
+        and the value of the state that earned the reward is learned before the lane is moved.  Plans without a learner
+        keep resetting before the populations are evaluated.  Such a plan never takes the one-launch step."""
         plan = self._agent.make_step_plan(neurons, capacity)
         return plan.attach_task(self, auto_reset=auto_reset, scripted_speed=scripted_speed)
 

@@ -21,9 +21,17 @@ riding in the gradient kernel (the traces are read once per step instead of twic
 The device copy of the weights is the master: `inputs[name]["w"]` READS them back (float64 `(n, n_in)`, a copy: edit
 it and assign it back, `inputs[name]["w"] = w`) and assigning replaces the device weights.
 
-Not supported (NotImplementedError): a learner inside `Agent.simulate()` or a step plan while `learning` is True (one
-weight update per step needs the step's reward; set `VN.learning = False` to freeze it — a frozen learner is a
-`FeedForwardLayer`), recurrent inputs, callable activations.  The learner is not sharded: `parallel.py` shards the agents
+A `StepPlan` (`Ag.make_step_plan()`, `env.make_step_plan()`) holds a learning learner: every plan step then ends with
+`learn(reward)` and, in a task plan with `auto_reset`, `reset(lanes=terminal)` — in that order, BEFORE the task resets the
+terminal lanes (plan.py: "learn, then reset") — as two launches behind the forward pass (riab_td_learn_step).  The reward
+is the task's, or a device tensor bound with `plan.bind_reward(VN, tensor)`.  The plan keeps the mode it recorded:
+flipping `learning` afterwards has no effect on it — rebuild the plan.  One deviation from the eager loop: a learner that
+keeps a history has its `firingrate` row IN the history, so the plan's reset leaves that row as recorded, where eager
+`reset()` zeroes a clone of it; only the host-visible `VN.firingrate` of a lane that has just been reset differs.
+
+Not supported (NotImplementedError): a learner inside `Agent.simulate()` or behind the unchanged `Ag.update(); N.update()`
+loop's native stepper while `learning` is True (one weight update per step needs the step's reward; set
+`VN.learning = False` to freeze it — a frozen learner is a `FeedForwardLayer`), recurrent inputs, callable activations.  The learner is not sharded: `parallel.py` shards the agents
 of a run over GPUs, and one learner fed by all of them would need a gradient all-reduce, the step path's first
 collective — an Agent that is a shard (`agent_id0 != 0`) is refused."""
 import copy
@@ -265,6 +273,18 @@ class ValueNeuron(FeedForwardLayer):
     def _population(self, plan_index=None):
         self._refuse_while_learning("a step plan")
         return super()._population(plan_index)
+
+    def _learner_record(self, plan_index):
+        """A LEARNING learner as a `StepPlan` records it: the feed-forward descriptor and the learner block of
+        riab_plan_set_learner — the persistent `_args()` structures (constants, traces) and `_workspace`."""
+        pop = FeedForwardLayer._population(self, plan_index)
+        p, arr, nl = self._args()
+        traces = (C.c_void_p * nl)(*[arr[l].trace for l in range(nl)])
+        return pop, {"params": p, "traces": traces, "reward": self._plan_reward(plan_index)}
+
+    def _plan_reward(self, plan_index):
+        """Where a plan finds this learner's reward when nobody binds one: `(kind, population index)`."""
+        return _L.REWARD_NONE, -1
 
     def _rates_from_trajectory(self, traj, out, t0, tc, step0, dt, stream):
         self._refuse_while_learning("Agent.simulate()")

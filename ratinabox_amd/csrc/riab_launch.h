@@ -92,6 +92,9 @@ int launch_bvc(const RiabEnv* env, const RiabRateIO* io, const double* test_dirs
                float* ray_out, const int32_t* cell_rows, const int32_t* windows, float* xch, uint32_t* xch_count,
                uint32_t* xch_arrivals, int n_cus, hipStream_t stream);
 
+// riab_td.hip: the checks of every riab_td_* entry point on a learner's constants and layers
+int td_check(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers);
+
 // riab_ovc.hip: the most objects the vector-cell kernel's LDS staging holds (-1: no device)
 int ovc_object_limit();
 

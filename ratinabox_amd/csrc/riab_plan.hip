@@ -14,6 +14,20 @@
 #include "riab_agent_kernel.h"
 #include "riab_launch.h"
 
+// A TD learner of the plan (riab_plan_set_learner): population `index` + what riab_td_learn_step takes beyond its rows
+struct PlanLearner {
+  int index;
+  RiabTDParams p;
+  float* trace[RIAB_FF_MAX_INPUTS];
+  float *v_last, *dvdt, *td, *workspace;
+  int64_t workspace_floats;
+  int reward_kind;  // RIAB_REWARD_*
+  const void* reward;
+  int reward_f64;
+  int64_t reward_ld_n, reward_ld_b;
+  int reward_index;
+};
+
 struct RiabPlan {
   RiabEnv env;
   RiabMotion motion;
@@ -36,6 +50,7 @@ struct RiabPlan {
   int32_t* diag;
   std::vector<RiabPopulation> pops;
   std::vector<int64_t> pop_fill;
+  std::vector<PlanLearner> learners;  // in the order of their populations
   // attached task (riab_plan_set_task) whose lanes may be the agents of one world (riab_plan_set_task_world): the record
   // its launchers take.  tk.t_env and tk.counter are cursors like `step`; hist_x/y and gv_x/y are set per step (task_run)
   bool has_task;
@@ -145,6 +160,7 @@ static int fused_task_step(RiabPlan* p, float* row, hipStream_t s, bool query) {
 static int plan_fused(RiabPlan* p, bool whole_step = false) {
   if (!p->sync_words || riab::g_options[RIAB_OPT_FUSED_STEP] == 0 || p->forced) return 0;
   if (p->has_task && (!whole_step || riab::g_options[RIAB_OPT_FUSED_TASK] == 0)) return 0;
+  if (p->has_task && !p->learners.empty()) return 0;  // (the TASK modes reset inside the kernel: a learner's step resets last)
   if (p->fused_n == -2 || p->fused_whole != whole_step) {
     p->fused_whole = whole_step;
     p->pre_misses.resize(p->pops.size(), 0);
@@ -427,6 +443,56 @@ extern "C" int riab_plan_set_task_world(RiabPlan* p, double* world, uint64_t* me
   return RIAB_OK;
 }
 
+extern "C" int riab_plan_set_learner(RiabPlan* p, int32_t index, const RiabTDParams* prm, float* const* traces, float* v_last,
+                                     float* dvdt, float* td, float* workspace, int64_t workspace_floats, int32_t reward_kind,
+                                     const void* reward, int32_t reward_f64, int64_t reward_ld_n, int64_t reward_ld_b,
+                                     int32_t reward_index) {
+  if (!p || !prm || !traces || index < 0 || index >= (int)p->pops.size()) return RIAB_EINVAL;
+  const RiabPopulation& q = p->pops[index];
+  if (q.kind != RIAB_POP_FF || !q.rates_prime) return RIAB_EINVAL;
+  if (prm->n != q.n || prm->Bp != p->B) return RIAB_EINVAL;
+  if (!v_last || !dvdt || !td || !workspace) return RIAB_EINVAL;
+  if (reward_kind < RIAB_REWARD_NONE || reward_kind > RIAB_REWARD_POPULATION) return RIAB_EINVAL;
+  PlanLearner L = {};
+  L.index = index;
+  L.p = *prm;
+  RiabTDLayer layers[RIAB_FF_MAX_INPUTS];
+  for (int l = 0; l < q.n_inputs; ++l) {  // (the rates are this step's rows, resolved per step: the check gets the trace's)
+    L.trace[l] = traces[l];
+    layers[l].rates = traces[l];
+    layers[l].trace = traces[l];
+    layers[l].wt = const_cast<float*>(q.input_wt[l]);
+    layers[l].n_in = p->pops[q.input_index[l]].n;
+  }
+  const int rc = riab::td_check(prm, layers, q.n_inputs);
+  if (rc) return rc;
+  if ((((uintptr_t)v_last | (uintptr_t)dvdt | (uintptr_t)td | (uintptr_t)workspace | (uintptr_t)q.rates_prime) & 15)) return RIAB_EALIGN;
+  if (workspace_floats < riab_td_workspace(prm, layers, q.n_inputs)) return RIAB_EINVAL;
+  if (reward_kind == RIAB_REWARD_POINTER) {
+    if (!reward || reward_ld_n < 0 || reward_ld_b < 0) return RIAB_EINVAL;
+    if (((uintptr_t)reward & (reward_f64 ? 7 : 3))) return RIAB_EALIGN;
+  }
+  if (reward_kind == RIAB_REWARD_POPULATION && (reward_index < 0 || reward_index >= index || p->pops[reward_index].n != q.n))
+    return RIAB_EINVAL;
+  L.v_last = v_last;
+  L.dvdt = dvdt;
+  L.td = td;
+  L.workspace = workspace;
+  L.workspace_floats = workspace_floats;
+  L.reward_kind = reward_kind;
+  L.reward = reward;
+  L.reward_f64 = reward_f64;
+  L.reward_ld_n = reward_ld_n;
+  L.reward_ld_b = reward_ld_b;
+  L.reward_index = reward_index;
+  size_t k = 0;  // (kept in the order of the populations; the same index again: the record is replaced)
+  while (k < p->learners.size() && p->learners[k].index < index) ++k;
+  if (k < p->learners.size() && p->learners[k].index == index) p->learners[k] = L;
+  else p->learners.insert(p->learners.begin() + k, L);
+  p->fused_n = -2;
+  return RIAB_OK;
+}
+
 extern "C" double riab_plan_task_clock(const RiabPlan* p) { return p && p->has_task ? p->tk.t_env : 0.0; }
 
 extern "C" int riab_plan_set_clock(RiabPlan* p, double t) {
@@ -599,6 +665,7 @@ static void advance_cursors(RiabPlan* p, bool task) {
 // the same kernels, arguments and counters as riab_plan_step, so the same results bit for bit.  No task attached.
 extern "C" int riab_plan_step_agent(RiabPlan* p, riab_stream_t stream) {
   if (!p || p->has_task) return RIAB_EINVAL;
+  if (!p->learners.empty()) return RIAB_EUNSUPPORTED;  // (a learner's stage belongs to whole steps: riab_plan_step)
   if (p->hist_base && p->hist_fill >= p->hist_cap) return RIAB_EFULL;
   const double* forced = nullptr;
   if (p->forced) {
@@ -646,6 +713,7 @@ extern "C" int riab_plan_discard_ahead(RiabPlan* p) {
 // Neurons.update() of population `index` on the agent's newest history row
 extern "C" int riab_plan_step_population(RiabPlan* p, int32_t index, riab_stream_t stream) {
   if (!p || p->has_task || index < 0 || index >= (int)p->pops.size()) return RIAB_EINVAL;
+  if (!p->learners.empty()) return RIAB_EUNSUPPORTED;
   const size_t i = (size_t)index;
   if (p->pops[i].capacity_rows > 0 && p->pop_fill[i] >= p->pops[i].capacity_rows) return RIAB_EFULL;
   if (p->hist_base && p->hist_fill == 0) return RIAB_EINVAL;  // no agent row written into this chunk yet
@@ -698,6 +766,23 @@ static int motion_stage(RiabPlan* p, float* row, hipStream_t s, int n_fused) {
     return RIAB_OK;
   }
   const bool scripted = p->has_task && p->tk.gv_scale > 0.0;
+  if (p->has_task && !p->learners.empty()) {
+    // a plan with a learner resets LAST (deferred_reset): the task's (or world's) step alone rides with the motion step —
+    // no reset, no next action — while the reset counter moves as in every step with auto_reset
+    riab::AgentArgs ma;
+    rc = riab::fill_agent_args(ma, &p->env, &p->motion, p->state, p->B, p->agent_id0, p->drift, nullptr, nullptr, nullptr,
+                               p->seed, p->step, 1, row, p->diag);
+    if (rc) return rc;
+    advance_cursors(p, true);
+    riab::TaskRun t = task_run(p, row);
+    t.auto_reset = 0;
+    t.gv_x = t.gv_y = nullptr;
+    rc = t.world ? riab::launch_motion_world(ma, t, s) : riab::launch_motion_task(ma, t, s);
+    if (rc) return rc;
+    p->launches += 1;
+    p->action_ready = false;
+    return RIAB_OK;
+  }
   if (n_fused > 0) {  // ... with the task's (or world's) step, its reset and the next action as well (TASK modes)
     advance_cursors(p, true);
     rc = fused_task_step(p, row, s, false);
@@ -768,8 +853,90 @@ static int rest_of_populations(RiabPlan* p, const float* row, hipStream_t s, boo
   return RIAB_OK;
 }
 
+// What a step with learners needs before anything is launched: every reward bound, and no learner whose row of the step
+// (its one scratch row: no history chunk) is zeroed by its reset before another learner has read it
+static int check_learners(const RiabPlan* p) {
+  for (const PlanLearner& L : p->learners) {
+    if (L.reward_kind == RIAB_REWARD_NONE || (L.reward_kind == RIAB_REWARD_TASK && !p->has_task)) return RIAB_EINVAL;
+    for (const PlanLearner& M : p->learners) {
+      if (M.index >= L.index || p->pops[M.index].capacity_rows > 0) continue;
+      const RiabPopulation& q = p->pops[L.index];
+      for (int l = 0; l < q.n_inputs; ++l)
+        if (q.input_index[l] == M.index) return RIAB_EUNSUPPORTED;
+      if (L.reward_kind == RIAB_REWARD_POPULATION && L.reward_index == M.index) return RIAB_EUNSUPPORTED;
+    }
+  }
+  return RIAB_OK;
+}
+
+// this step's row of population j, whose cursor points past it
+static float* row_of(const RiabPlan* p, int j) {
+  const RiabPopulation& q = p->pops[j];
+  const int64_t r = q.capacity_rows > 0 ? p->pop_fill[j] - 1 : 0;
+  return q.rates_base + r * q.n * p->B;
+}
+
+// `learn(reward)` of every learner on the rows the populations have just written and, with a task that resets on its
+// own, `reset(lanes = terminal)`: two launches per learner (riab_td_learn_step)
+static int learner_stage(RiabPlan* p, hipStream_t s) {
+  const uint8_t* const mask = p->has_task && p->tk.auto_reset ? p->tk.terminal_out : nullptr;
+  for (const PlanLearner& L : p->learners) {
+    const RiabPopulation& q = p->pops[L.index];
+    RiabTDLayer layers[RIAB_FF_MAX_INPUTS];
+    for (int l = 0; l < q.n_inputs; ++l) {
+      layers[l].rates = row_of(p, q.input_index[l]);
+      layers[l].trace = L.trace[l];
+      layers[l].wt = const_cast<float*>(q.input_wt[l]);
+      layers[l].n_in = p->pops[q.input_index[l]].n;
+    }
+    const void* reward = L.reward;
+    int f64 = L.reward_f64;
+    int64_t ld_n = L.reward_ld_n, ld_b = L.reward_ld_b;
+    if (L.reward_kind == RIAB_REWARD_TASK) {
+      reward = p->tk.reward_out;
+      f64 = 1;
+      ld_n = 0;
+      ld_b = 1;
+    } else if (L.reward_kind == RIAB_REWARD_POPULATION) {
+      reward = row_of(p, L.reward_index);
+      f64 = 0;
+      ld_n = p->B;
+      ld_b = 1;
+    }
+    const int rc = riab_td_learn_step(&L.p, layers, q.n_inputs, reward, f64, ld_n, ld_b, row_of(p, L.index), L.v_last, L.dvdt,
+                                      q.rates_prime, L.td, mask, q.capacity_rows == 0 ? 1 : 0, L.workspace, L.workspace_floats, s);
+    if (rc) return rc;
+    p->launches += (L.p.n > 256 ? 3 : 2);
+  }
+  return RIAB_OK;
+}
+
+// the reset a plan with a learner left for last: the caller's `env.reset(mask = terminal)`, decided on the device, on the
+// newest history row; the coming step's scripted action is first_action's (the world's reset writes it itself)
+static int deferred_reset(RiabPlan* p, float* row, hipStream_t s) {
+  if (!p->has_task || !p->tk.auto_reset) return RIAB_OK;
+  const riab::TaskRun& t = task_run(p, row);
+  int rc;
+  if (t.world) {
+    rc = riab_task_world_reset(&p->env, &t.task, t.task_state, t.world, t.task_B, t.agent_id0, t.t_env, t.n_select, t.ordered,
+                               t.seed, t.counter, t.teleport, nullptr, nullptr, t.pos_x, t.pos_y, t.hist_x, t.hist_y, t.ep_log,
+                               t.ep_log_cap, t.ep_count, 1, t.gv_scale, t.gv_x, t.gv_y, t.diag, s);
+    if (rc == RIAB_OK) p->action_ready = t.gv_scale > 0.0;
+  } else {
+    rc = riab_task_reset(&p->env, &t.task, t.task_state, t.terminal_out, t.task_B, t.agent_id0, t.t_env, t.n_select, t.ordered,
+                         t.seed, t.counter, t.teleport, nullptr, nullptr, t.pos_x, t.pos_y, t.hist_x, t.hist_y, t.ep_log,
+                         t.ep_log_cap, t.ep_count, t.diag, s);
+  }
+  if (rc == RIAB_OK) p->launches += 1;
+  return rc;
+}
+
 extern "C" int riab_plan_step(RiabPlan* p, int32_t n_steps, riab_stream_t stream) {
   if (!p || n_steps <= 0) return RIAB_EINVAL;
+  if (!p->learners.empty()) {
+    const int rc = check_learners(p);
+    if (rc) return rc;
+  }
   if (riab_plan_rows_free(p) < n_steps) return RIAB_EFULL;
   if (p->forced && (p->has_task || p->forced_rows - p->forced_fill < n_steps)) return p->has_task ? RIAB_EINVAL : RIAB_EFULL;
   hipStream_t s = (hipStream_t)stream;
@@ -780,6 +947,10 @@ extern "C" int riab_plan_step(RiabPlan* p, int32_t n_steps, riab_stream_t stream
     int rc = p->has_task && p->tk.gv_scale > 0.0 ? first_action(p, s) : RIAB_OK;
     if (!rc) rc = motion_stage(p, row, s, n_fused);
     if (!rc) rc = rest_of_populations(p, row, s, n_fused > 0);
+    if (!rc && !p->learners.empty()) {  // learn, then reset
+      rc = learner_stage(p, s);
+      if (!rc) rc = deferred_reset(p, row, s);
+    }
     if (rc) return rc;
   }
   return RIAB_OK;

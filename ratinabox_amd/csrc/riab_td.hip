@@ -19,7 +19,14 @@
 // read once per step.  Lanes b >= B are zeroed in LDS on both sides: padded lanes contribute nothing, whatever they hold.
 // The chunk's partial G goes to a workspace; td_combine_kernel adds the partials in a fixed order (no float atomics: a
 // run is bit-identical to the next) and applies the update to W^T [n_in][Mp], the layout riab_feedforward reads.
+//
+// riab_td_learn_step: a whole `learn(reward); reset(lanes = mask)` behind the forward pass in TWO launches, for the step
+// plan's learner stage.  DVDT: the gradient pass works dV/dt out from V and V_last on the fly (the workgroups that store
+// the TD error store it too; V_last is read by every workgroup of the grid, so it is not written there).
+// td_finish_kernel: td_combine_kernel's blocks, and behind them blocks that copy V to V_last and zero the columns of the
+// masked lanes.  Stream order is all the two launches rely on.
 #include "riab_device.h"
+#include "riab_launch.h"
 
 namespace riab {
 
@@ -51,6 +58,9 @@ struct TDGradArgs {
   int64_t r_ld_n, r_ld_b;
   const float *v, *dvdt, *prime;
   float* td;
+  const float* v_last;  // DVDT: dvdt_out = (v - v_last) / dt is worked out here ...
+  float* dvdt_out;      // ... and stored by the workgroups that store td
+  float dt;
   int n;
   int64_t B, Bp;
   int slabs_per_chunk;
@@ -61,6 +71,19 @@ struct TDCombineArgs {
   TDLayerArgs layer[TD_MAX_LAYERS];
   int n, Mp, n_chunks;
   float scale, decay;
+};
+
+// td_finish_kernel: the combine blocks [0, n_combine) = (cx, n, layers) flattened, then the blocks of the [n][Bp] rows
+// (V -> V_last, masked columns zeroed), then — with a mask — those of every layer's trace from tb0[l] on
+struct TDFinishArgs {
+  TDCombineArgs c;
+  int cx, n_combine;
+  int tb0[TD_MAX_LAYERS + 1];
+  float* v;  // zeroed in the masked columns when zero_v (the caller's row is not a history row)
+  float *v_last, *dvdt, *td;
+  const uint8_t* mask;
+  int zero_v;
+  int64_t B, Bp;
 };
 
 struct TDTailArgs {
@@ -85,6 +108,16 @@ __device__ __forceinline__ v4f trace_next(v4f phi, v4f e, float c_phi, float c_e
   return a + b;
 }
 
+// dVdt = (V - V_last) / dt and td = r + dVdt - V / tau: td_dvdt_kernel, td_grad_kernel and its DVDT form give the same bits
+__device__ __forceinline__ v4f dvdt_of(v4f v, v4f v_last, float dt) {
+#pragma clang fp contract(off)
+  return (v - v_last) / dt;
+}
+__device__ __forceinline__ float td_of(float r, float dvdt, float v, float tau) {
+#pragma clang fp contract(off)
+  return (r + dvdt) - v / tau;
+}
+
 __device__ __forceinline__ float reward_at(const TDGradArgs& a, int i, int64_t b) {
   const int64_t idx = (int64_t)i * a.r_ld_n + b * a.r_ld_b;
   return a.reward_f64 ? (float)static_cast<const double*>(a.reward)[idx] : static_cast<const float*>(a.reward)[idx];
@@ -94,7 +127,7 @@ struct TDSlab {
   v4f e[4], phi[4];
 };
 
-template <int MT, bool FUSE>
+template <int MT, bool FUSE, bool DVDT>
 __global__ __launch_bounds__(256) void td_grad_kernel(const TDGradArgs a) {
   __shared__ __align__(16) float s_e[TD_JB][TD_LD];
   __shared__ __align__(16) float s_g[MT * 32][TD_LD];
@@ -163,13 +196,19 @@ __global__ __launch_bounds__(256) void td_grad_kernel(const TDGradArgs a) {
       if (b < a.Bp) {
         const int64_t off = (int64_t)i * a.Bp + b;
         const v4f v = *reinterpret_cast<const v4f*>(a.v + off);
-        const v4f dv = *reinterpret_cast<const v4f*>(a.dvdt + off);
+        v4f dv;
+        if (DVDT) {
+          dv = dvdt_of(v, *reinterpret_cast<const v4f*>(a.v_last + off), a.dt);
+          if (writes_td) *reinterpret_cast<v4f*>(a.dvdt_out + off) = dv;
+        } else {
+          dv = *reinterpret_cast<const v4f*>(a.dvdt + off);
+        }
         const v4f pr = *reinterpret_cast<const v4f*>(a.prime + off);
         v4f td = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           if (b + k < a.B) {
-            td[k] = (reward_at(a, i, b + k) + dv[k]) - v[k] / a.tau;
+            td[k] = td_of(reward_at(a, i, b + k), dv[k], v[k], a.tau);
             g[k] = td[k] * pr[k];
           }
         }
@@ -218,11 +257,11 @@ __global__ __launch_bounds__(256) void td_grad_kernel(const TDGradArgs a) {
 // inputs x 4 chunk groups: thread (j, q) adds the chunks q, q + 4, q + 8, ... in that order (the loads do not depend on
 // the sum: eight are in flight), then the four group sums are added in the order 0, 1, 2, 3 — a fixed order, whatever
 // the machine does.
-__global__ __launch_bounds__(256) void td_combine_kernel(const TDCombineArgs a) {
+__device__ __forceinline__ void td_combine_block(const TDCombineArgs& a, int bx, int by, int bz) {
   __shared__ float s_part[4][64];
-  const TDLayerArgs& L = a.layer[blockIdx.z];
+  const TDLayerArgs& L = a.layer[bz];
   const int jl = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const int jj = blockIdx.x * 64 + jl, i = blockIdx.y;
+  const int jj = bx * 64 + jl, i = by;
   float g = 0.0f;
   if (jj < L.n_in) {
     const float* p = L.partial + (int64_t)i * L.n_in + jj;
@@ -239,6 +278,63 @@ __global__ __launch_bounds__(256) void td_combine_kernel(const TDCombineArgs a) 
     *w = w0 + (a.scale * sum - a.decay * w0);
   }
 }
+__global__ __launch_bounds__(256) void td_combine_kernel(const TDCombineArgs a) {
+  td_combine_block(a, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+
+// which of the quad's lanes b .. b + 3 are reset: b + k < B with mask[b + k] != 0
+__device__ __forceinline__ bool td_quad_hits(const uint8_t* mask, int64_t b, int64_t B, bool hit[4]) {
+  bool any = false;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    hit[k] = b + k < B && mask[b + k] != 0;
+    any |= hit[k];
+  }
+  return any;
+}
+__device__ __forceinline__ void td_zero_hits(float* rows, int64_t q, const bool hit[4]) {
+  v4f* const p = reinterpret_cast<v4f*>(rows) + q;
+  v4f x = *p;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) x[k] = hit[k] ? 0.0f : x[k];
+  *p = x;
+}
+
+// The second launch of riab_td_learn_step: td_combine_kernel's blocks (same sums, same order), then V_last = V and
+// ValueNeuron.reset(lanes = mask) — only quads with a masked lane are rewritten, as td_reset_kernel does.
+__global__ __launch_bounds__(256) void td_finish_kernel(const TDFinishArgs a) {
+  const int blk = blockIdx.x;  // block-uniform branches throughout
+  if (blk < a.n_combine) {
+    const int per_layer = a.cx * a.c.n;
+    const int bz = blk / per_layer, rest = blk - bz * per_layer;
+    td_combine_block(a.c, rest % a.cx, rest / a.cx, bz);
+    return;
+  }
+  const int tb = blk - a.n_combine;
+  const int64_t qpr = a.Bp / 4;
+  if (tb < a.tb0[0]) {  // the [n][Bp] rows
+    const int64_t q = (int64_t)tb * 256 + threadIdx.x;
+    if (q >= (int64_t)a.c.n * qpr) return;
+    bool hit[4] = {false, false, false, false};
+    const bool any = a.mask && td_quad_hits(a.mask, (q % qpr) * 4, a.B, hit);
+    v4f x = reinterpret_cast<const v4f*>(a.v)[q];
+    if (any) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) x[k] = hit[k] ? 0.0f : x[k];
+      if (a.zero_v) reinterpret_cast<v4f*>(a.v)[q] = x;
+      td_zero_hits(a.dvdt, q, hit);
+      td_zero_hits(a.td, q, hit);
+    }
+    reinterpret_cast<v4f*>(a.v_last)[q] = x;
+    return;
+  }
+  int l = 0;  // a trace (blocks exist only with a mask)
+  while (tb >= a.tb0[l + 1]) ++l;
+  const int64_t q = (int64_t)(tb - a.tb0[l]) * 256 + threadIdx.x;
+  if (q >= (int64_t)a.c.layer[l].n_in * qpr) return;
+  bool hit[4];
+  if (td_quad_hits(a.mask, (q % qpr) * 4, a.B, hit)) td_zero_hits(a.c.layer[l].trace, q, hit);
+}
 
 // dVdt = (V - V_last) / dt; V_last = V
 __global__ __launch_bounds__(256) void td_dvdt_kernel(const float* v, float* v_last, float* dvdt, int64_t quads, float dt) {
@@ -246,7 +342,7 @@ __global__ __launch_bounds__(256) void td_dvdt_kernel(const float* v, float* v_l
   if (q >= quads) return;
   const v4f x = reinterpret_cast<const v4f*>(v)[q];
   const v4f x0 = reinterpret_cast<const v4f*>(v_last)[q];
-  reinterpret_cast<v4f*>(dvdt)[q] = (x - x0) / dt;
+  reinterpret_cast<v4f*>(dvdt)[q] = dvdt_of(x, x0, dt);
   reinterpret_cast<v4f*>(v_last)[q] = x;
 }
 
@@ -282,7 +378,7 @@ __global__ __launch_bounds__(256) void td_reset_kernel(const TDResetArgs a) {
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
-static int td_check(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers) {
+int td_check(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers) {
   if (!p || !layers || n_layers <= 0) return RIAB_EINVAL;
   if (n_layers > TD_MAX_LAYERS) return RIAB_ETOOBIG;
   if (p->n <= 0 || p->B <= 0 || p->Bp < p->B || p->Mp % 32 != 0 || p->n > p->Mp) return RIAB_EINVAL;
@@ -333,10 +429,87 @@ static void td_launch_trace(const RiabTDParams* p, const RiabTDLayer* layers, in
   hipLaunchKernelGGL(td_trace_kernel, dim3((unsigned)((quads + 255) / 256), (unsigned)n_layers), dim3(256), 0, stream, t);
 }
 
+template <int MT, bool DVDT>
+static void td_launch_grad(const TDGradArgs& g, dim3 grid, bool fuse, hipStream_t stream) {
+  if (fuse) hipLaunchKernelGGL((td_grad_kernel<MT, true, DVDT>), grid, dim3(256), 0, stream, g);
+  else hipLaunchKernelGGL((td_grad_kernel<MT, false, DVDT>), grid, dim3(256), 0, stream, g);
+}
 template <int MT>
 static void td_launch_grad(const TDGradArgs& g, dim3 grid, bool fuse, hipStream_t stream) {
-  if (fuse) hipLaunchKernelGGL((td_grad_kernel<MT, true>), grid, dim3(256), 0, stream, g);
-  else hipLaunchKernelGGL((td_grad_kernel<MT, false>), grid, dim3(256), 0, stream, g);
+  if (g.v_last) td_launch_grad<MT, true>(g, grid, fuse, stream);
+  else td_launch_grad<MT, false>(g, grid, fuse, stream);
+}
+
+// The checks riab_td_update and riab_td_learn_step share, [the stand-alone trace kernel] and the gradient launch;
+// `c`: the arguments of the combine that follows.  v_last != null: dvdt is written here (the DVDT form), not read.
+static int td_gradient(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers, const void* reward,
+                       int32_t reward_f64, int64_t reward_ld_n, int64_t reward_ld_b, const float* v, const float* v_last,
+                       float* dvdt, const float* prime, float* td, int32_t fuse_trace, float* workspace,
+                       int64_t workspace_floats, hipStream_t stream, TDCombineArgs& c, int* widest_out) {
+  const int rc = td_check(p, layers, n_layers);
+  if (rc != RIAB_OK) return rc;
+  if (!reward || !v || !dvdt || !prime || !td || !workspace || reward_ld_n < 0 || reward_ld_b < 0) return RIAB_EINVAL;
+  if ((((uintptr_t)v | (uintptr_t)v_last | (uintptr_t)dvdt | (uintptr_t)prime | (uintptr_t)td | (uintptr_t)workspace) & 15))
+    return RIAB_EALIGN;
+  if (((uintptr_t)reward & (reward_f64 ? 7 : 3))) return RIAB_EALIGN;
+  if (workspace_floats < riab_td_workspace(p, layers, n_layers)) return RIAB_EINVAL;
+  TDGradArgs g = {};
+  c = {};
+  const int n_chunks = td_chunks(p, layers, n_layers, &g.slabs_per_chunk);
+  int jb = 0, widest = 0;
+  float* part = workspace;
+  for (int l = 0; l < n_layers; ++l) {
+    TDLayerArgs& L = g.layer[l];
+    L.rates = layers[l].rates;
+    L.trace = layers[l].trace;
+    L.wt = layers[l].wt;
+    L.partial = part;
+    L.n_in = layers[l].n_in;
+    L.jb0 = jb;
+    c.layer[l] = L;
+    jb += (layers[l].n_in + TD_JB - 1) / TD_JB;
+    part += (int64_t)n_chunks * p->n * layers[l].n_in;
+    widest = layers[l].n_in > widest ? layers[l].n_in : widest;
+  }
+  g.n_layers = n_layers;
+  g.reward = reward;
+  g.reward_f64 = reward_f64;
+  g.r_ld_n = reward_ld_n;
+  g.r_ld_b = reward_ld_b;
+  g.v = v;
+  g.dvdt = dvdt;
+  g.prime = prime;
+  g.td = td;
+  g.v_last = v_last;
+  g.dvdt_out = dvdt;
+  g.dt = p->dt;
+  g.n = p->n;
+  g.B = p->B;
+  g.Bp = p->Bp;
+  g.tau = p->tau;
+  td_trace_coefficients(p, &g.c_phi, &g.c_e);
+  // all row tiles of g in one workgroup (up to 8: 128 accumulator registers); wider learners take several row groups,
+  // and then the trace is updated by its own kernel first (two groups must not both rewrite it)
+  const int tiles = p->Mp / 32 < (p->n + 31) / 32 ? p->Mp / 32 : (p->n + 31) / 32;
+  const int mt = tiles <= 1 ? 1 : (tiles <= 2 ? 2 : (tiles <= 4 ? 4 : 8));
+  const int groups = (tiles + mt - 1) / mt;
+  bool fuse = fuse_trace != 0;
+  if (fuse && groups > 1) {
+    td_launch_trace(p, layers, n_layers, stream);
+    fuse = false;
+  }
+  const dim3 grid((unsigned)jb, (unsigned)n_chunks, (unsigned)groups);
+  if (mt == 1) td_launch_grad<1>(g, grid, fuse, stream);
+  else if (mt == 2) td_launch_grad<2>(g, grid, fuse, stream);
+  else if (mt == 4) td_launch_grad<4>(g, grid, fuse, stream);
+  else td_launch_grad<8>(g, grid, fuse, stream);
+  c.n = p->n;
+  c.Mp = p->Mp;
+  c.n_chunks = n_chunks;
+  c.scale = (float)((double)p->dt * (double)p->eta / (double)p->B);
+  c.decay = (float)((double)p->eta * (double)p->dt * (double)p->L2);
+  *widest_out = widest;
+  return RIAB_OK;
 }
 
 }  // namespace riab
@@ -373,66 +546,51 @@ extern "C" int riab_td_update(const RiabTDParams* p, const RiabTDLayer* layers, 
                               int32_t reward_f64, int64_t reward_ld_n, int64_t reward_ld_b, const float* v,
                               const float* dvdt, const float* prime, float* td, int32_t fuse_trace, float* workspace,
                               int64_t workspace_floats, riab_stream_t stream) {
-  const int rc = td_check(p, layers, n_layers);
+  TDCombineArgs c;
+  int widest;
+  const int rc = td_gradient(p, layers, n_layers, reward, reward_f64, reward_ld_n, reward_ld_b, v, nullptr,
+                             const_cast<float*>(dvdt), prime, td, fuse_trace, workspace, workspace_floats, (hipStream_t)stream, c,
+                             &widest);
   if (rc != RIAB_OK) return rc;
-  if (!reward || !v || !dvdt || !prime || !td || !workspace || reward_ld_n < 0 || reward_ld_b < 0) return RIAB_EINVAL;
-  if ((((uintptr_t)v | (uintptr_t)dvdt | (uintptr_t)prime | (uintptr_t)td | (uintptr_t)workspace) & 15)) return RIAB_EALIGN;
-  if (((uintptr_t)reward & (reward_f64 ? 7 : 3))) return RIAB_EALIGN;
-  if (workspace_floats < riab_td_workspace(p, layers, n_layers)) return RIAB_EINVAL;
-  TDGradArgs g = {};
-  TDCombineArgs c = {};
-  const int n_chunks = td_chunks(p, layers, n_layers, &g.slabs_per_chunk);
-  int jb = 0, widest = 0;
-  float* part = workspace;
-  for (int l = 0; l < n_layers; ++l) {
-    TDLayerArgs& L = g.layer[l];
-    L.rates = layers[l].rates;
-    L.trace = layers[l].trace;
-    L.wt = layers[l].wt;
-    L.partial = part;
-    L.n_in = layers[l].n_in;
-    L.jb0 = jb;
-    c.layer[l] = L;
-    jb += (layers[l].n_in + TD_JB - 1) / TD_JB;
-    part += (int64_t)n_chunks * p->n * layers[l].n_in;
-    widest = layers[l].n_in > widest ? layers[l].n_in : widest;
-  }
-  g.n_layers = n_layers;
-  g.reward = reward;
-  g.reward_f64 = reward_f64;
-  g.r_ld_n = reward_ld_n;
-  g.r_ld_b = reward_ld_b;
-  g.v = v;
-  g.dvdt = dvdt;
-  g.prime = prime;
-  g.td = td;
-  g.n = p->n;
-  g.B = p->B;
-  g.Bp = p->Bp;
-  g.tau = p->tau;
-  td_trace_coefficients(p, &g.c_phi, &g.c_e);
-  // all row tiles of g in one workgroup (up to 8: 128 accumulator registers); wider learners take several row groups,
-  // and then the trace is updated by its own kernel first (two groups must not both rewrite it)
-  const int tiles = p->Mp / 32 < (p->n + 31) / 32 ? p->Mp / 32 : (p->n + 31) / 32;
-  const int mt = tiles <= 1 ? 1 : (tiles <= 2 ? 2 : (tiles <= 4 ? 4 : 8));
-  const int groups = (tiles + mt - 1) / mt;
-  bool fuse = fuse_trace != 0;
-  if (fuse && groups > 1) {
-    td_launch_trace(p, layers, n_layers, (hipStream_t)stream);
-    fuse = false;
-  }
-  const dim3 grid((unsigned)jb, (unsigned)n_chunks, (unsigned)groups);
-  if (mt == 1) td_launch_grad<1>(g, grid, fuse, (hipStream_t)stream);
-  else if (mt == 2) td_launch_grad<2>(g, grid, fuse, (hipStream_t)stream);
-  else if (mt == 4) td_launch_grad<4>(g, grid, fuse, (hipStream_t)stream);
-  else td_launch_grad<8>(g, grid, fuse, (hipStream_t)stream);
-  c.n = p->n;
-  c.Mp = p->Mp;
-  c.n_chunks = n_chunks;
-  c.scale = (float)((double)p->dt * (double)p->eta / (double)p->B);
-  c.decay = (float)((double)p->eta * (double)p->dt * (double)p->L2);
   hipLaunchKernelGGL(td_combine_kernel, dim3((unsigned)((widest + 63) / 64), (unsigned)p->n, (unsigned)n_layers), dim3(256),
                      0, (hipStream_t)stream, c);
+  return (int)hipGetLastError();
+}
+
+extern "C" int riab_td_learn_step(const RiabTDParams* p, const RiabTDLayer* layers, int32_t n_layers, const void* reward,
+                                  int32_t reward_f64, int64_t reward_ld_n, int64_t reward_ld_b, float* v, float* v_last,
+                                  float* dvdt, const float* prime, float* td, const uint8_t* mask, int32_t zero_v,
+                                  float* workspace, int64_t workspace_floats, riab_stream_t stream) {
+  if (!v_last) return RIAB_EINVAL;
+  // (what the finish launch's flat grid holds is checked before the gradient is launched)
+  int rc = td_check(p, layers, n_layers);
+  if (rc != RIAB_OK) return rc;
+  TDFinishArgs f = {};
+  int widest = 0;
+  for (int l = 0; l < n_layers; ++l) widest = layers[l].n_in > widest ? layers[l].n_in : widest;
+  f.cx = (widest + 63) / 64;
+  const int64_t qpr = p->Bp / 4;
+  int64_t blocks = (int64_t)f.cx * p->n * n_layers;
+  if (blocks > INT32_MAX / 2) return RIAB_ETOOBIG;
+  f.n_combine = (int)blocks;
+  int64_t tb = (p->n * qpr + 255) / 256;
+  for (int l = 0; l <= n_layers; ++l) {
+    if (blocks + tb > INT32_MAX / 2) return RIAB_ETOOBIG;
+    f.tb0[l] = (int)tb;
+    if (l < n_layers && mask) tb += (layers[l].n_in * qpr + 255) / 256;
+  }
+  rc = td_gradient(p, layers, n_layers, reward, reward_f64, reward_ld_n, reward_ld_b, v, v_last, dvdt, prime, td, 1, workspace,
+                   workspace_floats, (hipStream_t)stream, f.c, &widest);
+  if (rc != RIAB_OK) return rc;
+  f.v = v;
+  f.v_last = v_last;
+  f.dvdt = dvdt;
+  f.td = td;
+  f.mask = mask;
+  f.zero_v = zero_v;
+  f.B = p->B;
+  f.Bp = p->Bp;
+  hipLaunchKernelGGL(td_finish_kernel, dim3((unsigned)(f.n_combine + tb)), dim3(256), 0, (hipStream_t)stream, f);
   return (int)hipGetLastError();
 }
 

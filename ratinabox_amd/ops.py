@@ -18,6 +18,7 @@ Functional operators (return a new tensor)
 In-place operators
     td_forward_tail  the tail of ValueNeuron.update(): dV/dt, V_last and (optionally) the eligibility traces
     td_update        ValueNeuron.update_weights(reward): TD error, batch-mean gradient on the matrix cores, W^T updated
+    td_learn_step    ValueNeuron.learn(reward) behind the forward pass + reset(lanes=mask), in two launches
     agent_step_      T fused Agent.update() steps on the float64 state (12, B); writes the history rows
     simulate_        T x (Agent.update(); N.update() for N in populations) as ONE native call (riab_simulate): the state,
                      the trajectory rows and every population's rate / spike rows are written
@@ -338,6 +339,33 @@ def td_update(weights_t: List[Tensor], traces: List[Tensor], rates: List[Tensor]
     _L.check(_L.lib.riab_td_update(p, arr, len(rates), _L.ptr(reward), 1 if reward.dtype == torch.float64 else 0, ld_n, ld_b,
                                    _L.ptr(v), _L.ptr(dvdt), _L.ptr(prime), _L.ptr(td), 1 if fuse_trace else 0,
                                    _L.ptr(workspace), int(workspace.numel()), _L.current_stream()), "riab_td_update")
+
+
+@_register("td_learn_step(Tensor(a!)[] weights_t, Tensor(b!)[] traces, Tensor[] rates, Tensor reward, Tensor(c!) v, "
+           "Tensor(d!) v_last, Tensor(e!) dvdt, Tensor prime, Tensor(f!) td, Tensor? mask, bool zero_v, Tensor(g!) workspace, "
+           "float[] consts, int B) -> ()",
+           lambda weights_t, traces, rates, reward, v, v_last, dvdt, prime, td, mask, zero_v, workspace, consts, B: None)
+def td_learn_step(weights_t: List[Tensor], traces: List[Tensor], rates: List[Tensor], reward: Tensor, v: Tensor,
+                  v_last: Tensor, dvdt: Tensor, prime: Tensor, td: Tensor, mask: Optional[Tensor], zero_v: bool,
+                  workspace: Tensor, consts: List[float], B: int) -> None:
+    """`td_forward_tail(with_trace=False)`, `td_update(fuse_trace=True)` and ValueNeuron.reset(lanes=mask) in two launches
+    (riab_td_learn_step), in place and with the same bits: dvdt = (v - v_last) / dt is worked out inside the gradient pass,
+    the finish launch adds the partial sums, copies v to v_last and zeroes the columns b < B with mask[b] != 0 of the traces,
+    v_last, dvdt, td and — `zero_v` only — v.  mask: uint8 / bool (>= B,) or None (no reset).  Other arguments as `td_update`."""
+    n, Bp = int(v.shape[0]), int(v.shape[1])
+    for name, t in (("v", v), ("v_last", v_last), ("dvdt", dvdt), ("prime", prime), ("td", td)):
+        _td_rows(t, n, Bp, name)
+    p, arr = _td_structs(n, B, Bp, consts, rates, traces, weights_t)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous float32 tensor")
+    if mask is not None and (mask.dtype not in (torch.uint8, torch.bool) or mask.dim() != 1 or not mask.is_contiguous()
+                             or mask.shape[0] < int(B)):
+        raise ValueError(f"mask must be a contiguous uint8 or bool tensor of at least B = {int(B)} lanes")
+    ld_n, ld_b = _reward_strides(reward, n, int(B), Bp)
+    _L.check(_L.lib.riab_td_learn_step(p, arr, len(rates), _L.ptr(reward), 1 if reward.dtype == torch.float64 else 0, ld_n,
+                                       ld_b, _L.ptr(v), _L.ptr(v_last), _L.ptr(dvdt), _L.ptr(prime), _L.ptr(td), _L.ptr(mask),
+                                       1 if zero_v else 0, _L.ptr(workspace), int(workspace.numel()), _L.current_stream()),
+             "riab_td_learn_step")
 
 
 # ---- Agent.update ----------------------------------------------------------------------------------------------

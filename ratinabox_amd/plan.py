@@ -14,6 +14,17 @@ parameters follow the dt of the step, as update() reads Agent.dt), FeedForwardLa
 their input layers are recorded before them (weights are read from the device copies made when the plan is built:
 rebuild the plan after editing `inputs[...]["w"]`).
 
+A `StepPlan` also holds LEARNING TD learners (contribs.ValueNeuron / SuccessorFeatures): the step then ends with a learner
+stage, and the order of a step becomes "learn, then reset" —
+
+    [scripted action], Agent.update, the task's step (reward, terminal), every population in list order (a learner's
+    forward pass included), learn(reward) of every learner, reset(lanes=terminal) of every learner and the task's reset of
+    the terminal lanes (both with a task and `auto_reset` only)
+
+— the order of examples/value_learning_example.py: the value of the state that earned the reward is learned before the
+lane is teleported.  Plans WITHOUT a learner keep today's order (the task resets before the populations are evaluated).
+The learner's weights are its device master copy, which the plan updates in place; `sync()` needs nothing new.
+
 Who owns what:
   `_NativePlan`  the `riab_plan_*` handle and everything that runs once per plan, attach, sync or close: recording the
                  agent and its populations, opening history rows (`_open_agent_rows`, `_open_pop_rows`: the scratch row
@@ -180,12 +191,29 @@ class _ForcedRows:
         self.left -= n
 
 
+def _reward_binding(reward, n, B, Bp, device=None):
+    """What `bind_reward` accepts: a torch tensor, float32 or float64, in any shape `update_weights` takes (a scalar,
+    `(n,)`, `(B,)` or `(n, B)`, B the agents or the padded batch) — `(is float64, stride over neurons, stride over
+    lanes)`; ValueError otherwise.  `device`: where it must live (the plan reads it in place every step)."""
+    from .ops import _reward_strides
+    if not torch.is_tensor(reward):
+        raise ValueError("the reward of a plan's learner must be a persistent torch tensor on the device (read in place)")
+    if reward.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"the reward must be float32 or float64, got {reward.dtype}")
+    if device is not None and (reward.device.type != device.type or
+                               (device.index is not None and reward.device.index != device.index)):
+        raise ValueError(f"the reward must live on {device}, got {reward.device}")
+    ld_n, ld_b = _reward_strides(reward, n, B, Bp)
+    return (1 if reward.dtype == torch.float64 else 0), ld_n, ld_b
+
+
 class _NativePlan:
     """One `riab_plan_*` handle and what both ways of driving it share: recording the agent and its populations,
     handing history rows to the plan, publishing the rows it wrote, closing.  Everything here runs once per plan, attach,
     sync or close; the per-step paths are the subclasses' own."""
 
     serves_updates = False    # True: Agent.update() / Neurons.update() are served from this plan (AutoStepper)
+    holds_learners = False    # True: a learning TD learner is recorded with its learner stage (StepPlan)
 
     def __init__(self, agent, neurons, forced_block=None):
         self.agent = agent
@@ -212,19 +240,38 @@ class _NativePlan:
         self._raw_stream = raw if raw is not None else (lambda _i: torch.cuda.current_stream().cuda_stream)
         self._dev_index = agent._device_index
         self._index, self._pops = {}, []     # {population: its index in the plan}; the descriptors, kept alive
+        self._learners = {}                  # {learner: [plan index, learner block, reward kind, bound reward tensor]}
         for N in self.neurons:
-            pop = N._population(self._index)          # (raises NotImplementedError for populations a plan cannot hold)
+            block = None
+            if self.holds_learners and getattr(N, "learning", False) and hasattr(N, "_learner_record"):
+                pop, block = N._learner_record(self._index)
+            else:
+                pop = N._population(self._index)      # (raises NotImplementedError for populations a plan cannot hold)
             N._plan_scratch(pop)
             idx = _L.lib.riab_plan_add(self._h, pop)
             if idx < 0:
                 raise _L.RiabError(f"riab_plan_add failed: {_L.strerror(idx)}")
             self._index[N] = idx
             self._pops.append(pop)
+            if block is not None:
+                self._learners[N] = [idx, block, block["reward"][0], None]
+                self._set_learner(N)
         _attach_fused(self, agent)
         self._agent_rows = None
         self._pop_rows = [None] * len(self.neurons)
         self._scratch_rates = [None] * len(self.neurons)
         agent._plan = self
+
+    def _set_learner(self, N):
+        """(Re-)record learner N's block and reward source with the native plan (riab_plan_set_learner)."""
+        idx, block, kind, r = self._learners[N]
+        f64 = ld_n = ld_b = 0
+        if kind == _L.REWARD_POINTER:
+            f64, ld_n, ld_b = _reward_binding(r, int(N.n), N._B, N._Bp, N._device)
+        ws = N._workspace
+        _L.check(_L.lib.riab_plan_set_learner(self._h, idx, block["params"], block["traces"], _L.ptr(N._v_last), _L.ptr(N._dvdt),
+                                              _L.ptr(N._td), _L.ptr(ws), int(ws.numel()), kind, _L.ptr(r), f64, ld_n, ld_b,
+                                              int(block["reward"][1])), "riab_plan_set_learner")
 
     # ---- history rows: opened (not yet history), handed to the plan ---------------------------------
     def _open_agent_rows(self, cap, full=None):
@@ -319,9 +366,12 @@ class StepPlan(_NativePlan):
     """`plan.step(n)`: n steps of the agent and every recorded population in one native call.  ONE pending counter and
     ONE list of clocks for all histories, which therefore open the same number of rows."""
 
+    holds_learners = True
+
     def __init__(self, agent, neurons=None, capacity=1024):
         self.capacity = int(capacity)
         super().__init__(agent, agent.Neurons if neurons is None else neurons, forced_block=self.capacity)
+        self._learner_dt = agent.dt   # (the learners' constants were recorded at this dt)
         self._drift_key = None
         self._drift_t = None
         self._step_fn = _L.lib.riab_plan_step
@@ -362,7 +412,13 @@ class StepPlan(_NativePlan):
         kernel the task kernel updates rewards / goals of all lanes; with `auto_reset` the lanes that
         became terminal are reset right away (the caller's `if terminal: env.reset()`), before the
         populations are evaluated.  `scripted_speed`: the action of every step is
-        `scripted_speed * unit goal vector`, computed on the device (no policy on the host)."""
+        `scripted_speed * unit goal vector`, computed on the device (no policy on the host).
+
+        A plan that holds a learning learner (contribs.ValueNeuron / SuccessorFeatures) LEARNS, THEN RESETS: the
+        populations are evaluated at the positions the task's step saw, every learner learns from the step's reward — the
+        task's, for a ValueNeuron nobody bound another one to (`bind_reward`) — and only then are the terminal lanes reset:
+        the learners' (`reset(lanes=terminal)`) and the task's, which still patches the newest history row.  Without
+        `auto_reset` the learner learns and the plan resets nothing."""
         ag = self.agent
         assert env._agent is ag, "the plan's agent is not the one added to this TaskEnvironment"
         task = env._task_struct()
@@ -380,6 +436,24 @@ class StepPlan(_NativePlan):
             _L.check(_L.lib.riab_plan_set_task_world(self._h, _L.ptr(env._world), _L.ptr(env._met), _L.ptr(env._cand),
                                                      _L.ptr(env._ticket)), "riab_plan_set_task_world")
         self._drift_key = None
+        for N, rec in self._learners.items():   # a ValueNeuron without a reward of its own takes the task's
+            if rec[2] == _L.REWARD_NONE:
+                rec[2] = _L.REWARD_TASK
+                self._set_learner(N)
+        return self
+
+    def bind_reward(self, learner, reward):
+        """The reward a ValueNeuron of this plan learns from: a persistent device tensor, float32 or float64, in any shape
+        `update_weights` accepts — a scalar, `(n,)`, `(B,)` or `(n, B)`.  It is read IN PLACE by every step: write into
+        it between `step()` calls.  Overrides the task's reward of a task plan."""
+        rec = self._learners.get(learner)
+        if rec is None:
+            raise ValueError(f"{getattr(learner, 'name', learner)} is not a learning learner of this plan")
+        if rec[1]["reward"][0] == _L.REWARD_POPULATION:
+            raise ValueError(f"{learner.name} learns from its features: it takes no other reward")
+        _reward_binding(reward, int(learner.n), learner._B, learner._Bp, learner._device)
+        rec[2], rec[3] = _L.REWARD_POINTER, reward
+        self._set_learner(learner)
         return self
 
     # ---- stepping --------------------------------------------------------------------------------
@@ -398,6 +472,12 @@ class StepPlan(_NativePlan):
             raise RuntimeError("this plan was closed (the agent was stepped eagerly, its history reset or an object added to "
                                "its environment): make a new one")
         dt = dt or ag.dt
+        if self._learners:
+            for N, rec in self._learners.items():
+                if rec[2] == _L.REWARD_NONE:
+                    raise ValueError(f"{N.name} has no reward in this plan: plan.bind_reward({N.name}, tensor), or attach a task")
+            if dt != self._learner_dt:
+                raise ValueError("the plan's learners were recorded at another dt: rebuild the plan")
         if self._task_env is not None:
             # actions land in the plan's persistent drift buffer: no per-step parameter resolution
             has_drift = drift_velocity is not None or self._scripted
