@@ -30,6 +30,15 @@
 // rate_kernel_wide evaluates them.  Bit-identical to the two-launch step (tests/test_gpu_step1.py).
 // [MI355X] cfg 2 (4096 agents x 1024 PlaceCells): 9.0-9.2 us per step against 13.7; where it goes and what was tried:
 // DESIGN.md 3.9, docs/EXPERIMENTS.md r05.
+//
+// Map of the device code, in file order: s1_group / s1_group_few / s1_group_any (one cell group of one population) —
+// the stages of the step: s1_sync_rewards_ready / s1_sync_draws_ready / s1_sync_lists_ready (the writer's three LDS
+// hand-overs by name), s1_world_prefetch, s1_store_state (the write-back's stores), s1_draw_normals, s1_motion_back (the
+// motion step's second half), s1_helper_rewards / s1_helper_draws (the helper waves' share of a replica task's books),
+// s1_world_reset, s1_store_history, s1_rates_pass (a wave's cell groups), s1_world_second_pass — the role x barrier
+// table — step1_body, the schedule: LDS arrays, role predicates, the polling lambdas (pick, arrivals, wait_arrivals,
+// world_verdict, write_back, rates_few) and the pieces that change the kernels' code when moved (docs/EXPERIMENTS.md
+// r08-1) — kernarg_warm, the two kernels — the host side.
 #include <map>
 #include <mutex>
 #include <utility>
@@ -151,7 +160,7 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 //   * What a lane's bookkeeping writes where other workgroups read (the position, the next action in the drift
 //     buffer) is stored behind the arrival words.
 // Workgroups y >= 1 now wait for the writer's verdict, which the writer posts without waiting for anybody: no cycle, but
-// the grid has to be resident at once (launch_step1_cell refuses shapes that are not); bounded by the same spin limit
+// the grid has to be resident at once (launch_step1_impl refuses shapes that are not); bounded by the same spin limit
 // and counter as the state write-back.
 struct Step1Task {
   TaskArgs a;
@@ -315,6 +324,259 @@ __device__ __forceinline__ void s1_group_any(const Step1Pops& ps, const Step1Pop
 #undef RIAB_S1_RUN
 }
 
+// ---- the stages of the step ---------------------------------------------------------------------------------------
+// step1_body, below, is their schedule: it declares the LDS arrays, the role predicates and the lambdas that poll, and
+// calls the stages in order, with every barrier in its own text.  A stage is a free function, inlined, that takes what
+// it reads by value or const&, what it advances by reference, and starts with RIAB_EXACT_FP like the body it was cut
+// from (contraction would change bits).  What the comparison of the kernels' assembly allowed, and what it did not:
+// docs/EXPERIMENTS.md r08-1.
+
+// The three hand-overs through LDS between the mover and the helper waves of a replica task's writer: producer and
+// consumer call the same name, once each (the role x barrier table in front of step1_body)
+__device__ __forceinline__ void s1_sync_rewards_ready() { lds_barrier(); }  // helpers' rewards_step -> movers' goal checks
+__device__ __forceinline__ void s1_sync_draws_ready() { lds_barrier(); }    // helpers' reset_draw -> movers' reset
+__device__ __forceinline__ void s1_sync_lists_ready() { lds_barrier(); }    // movers' lists and positions -> helpers' next action
+
+// (one world, writer) the world's list as this step finds it, the lane's reward rows: one batch with the state
+__device__ __forceinline__ void s1_world_prefetch(const Step1Task& tk, const int64_t b, const int tid, const bool wlive,
+                                                  WorldShared& s_world, WorldLaneIn& win, double& pad_start0, uint8_t& terminal_prev) {
+  if (tid < RIAB_TASK_MAX_GOALS) s_world.list[tid] = (uint8_t)((int)tk.world[RIAB_TW_GOAL_LIST + tid] & 0xFF);
+  if (tid == 0) s_world.n = (int)tk.world[RIAB_TW_N_GOALS];
+  pad_start0 = tk.world[RIAB_TW_PAD_START];
+  terminal_prev = tk.world[RIAB_TW_TERMINAL] != 0.0 ? 1 : 0;
+  if (wlive) win = world_lane_load(tk.a, b);
+}
+
+// (the writer) agent b's float64 state back in place (`st`: its column of the state's twelve rows), with the step's
+// diagnostics: behind its wait for the segment's other workgroups
+__device__ __forceinline__ void s1_store_state(const AgentArgs& a, double* const st, const double px, const double py, const double vx,
+                                               const double vy, const double rot, const double mvx, const double mvy, const double mrot,
+                                               const double hx, const double hy, const double dist, const double dwall, const int n_bounce,
+                                               const int n_sat, const int n_bc, const int n_still) {
+  const int64_t B = a.B;
+  st[0 * B] = px;
+  st[1 * B] = py;
+  st[2 * B] = vx;
+  st[3 * B] = vy;
+  st[4 * B] = rot;
+  st[5 * B] = mvx;
+  st[6 * B] = mvy;
+  st[7 * B] = mrot;
+  st[8 * B] = hx;
+  st[9 * B] = hy;
+  st[10 * B] = dist;
+  st[11 * B] = dwall;
+  if (a.diag) {
+    if (n_bounce) atomicAdd(a.diag + 0, n_bounce);
+    if (n_sat) atomicAdd(a.diag + 1, n_sat);
+    if (n_bc) atomicAdd(a.diag + 2, n_bc);
+    if (n_still) atomicAdd(a.diag + 3, n_still);
+  }
+}
+
+// (helper waves) the step's two standard normals of agent `aid`, into LDS
+__device__ __forceinline__ void s1_draw_normals(const AgentArgs& a, const uint32_t aid, const int tid, float (&s_z)[2][256]) {
+  u32x4 pw = {0u, 0u, 0u, 0u};
+  const MotionDraw d = motion_normals(a.step0, true, aid, a.k0, a.k1, pw);
+  s_z[0][tid & 255] = d.z_rot;
+  s_z[1][tid & 255] = d.z_spd;
+}
+
+// (mover waves) the other half, on the normals the helper waves left in LDS: the velocity's update, the proposed step,
+// collisions, the output-only tail
+__device__ __forceinline__ void s1_motion_back(const AgentArgs& a, const TailConst<double>& tail_c, const MotionConst<double>& K,
+                                               const Wall<double>* s_w, const double* s_h, const float (&s_z)[2][256],
+                                               const NearWalls<double>& near, const WallPush<double>& push, const double ispeed,
+                                               double nv64, const double ppx, const double ppy, const bool zero_v, const double drx,
+                                               const double dry, const int64_t b, const uint32_t aid, const int tid, double& px,
+                                               double& py, double& vx, double& vy, double& rot, double& mvx, double& mvy, double& mrot,
+                                               double& hx, double& hy, double& dist, int& n_bounce, int& n_sat, int& n_bc, int& n_still) {
+  RIAB_EXACT_FP
+  const RiabMotion& m = a.m;
+  const double dt = m.dt;
+  const int nw = a.n_walls;
+  const lds_cf64_ptr lds_h = (lds_cf64_ptr)s_h;
+  const double z_rot = (double)s_z[0][tid], z_spd = (double)s_z[1][tid];
+  rot = ou_step<double>(rot, m.rot_theta_kw, m.rot_drift_kw, m.rot_sigma_kw, dt, z_rot);
+  {
+    double sn, cs;
+    sincos_small(rot * dt, &sn, &cs);
+    rotate_by<double>(cs, sn, vx, vy);
+    vx = zero_v ? 1e-8 : vx;
+    vy = zero_v ? 0.0 : vy;
+  }
+  // the speed's OU step in normal space and normal_to_rayleigh (utils.py:409-413)
+  nv64 = ou_step<double>(nv64, m.speed_theta_kw, 0.0, m.speed_sigma_kw, m.dt, z_spd);
+  const bool h_in_table = fabs(nv64) < RIAB_H_NMAX;
+  const SegRow<RIAB_H_DEG> hrow = seg_fetch<RIAB_H_DEG>(lds_h + seg_H(nv64) * RIAB_H_STRIDE);
+  double speed_new;
+  {
+    const double tnew = h_in_table ? seg_eval<RIAB_H_DEG>(hrow, nv64) : sqrt(-2.0 * log(1.0 - normcdf(nv64)));
+    speed_new = m.speed_mean_kw * tnew;
+  }
+  if (m.speed_std_is_zero) speed_new = K.sm_kw;
+  {
+    const double f = speed_new * ispeed;
+    vx *= f;
+    vy *= f;
+  }
+  // ---- _drift_velocity_update (Agent.py:331-341)
+  if (m.has_drift) drift_update<double>(m.drift_theta, drx, dry, dt, vx, vy);
+  // ---- _wall_velocity_update, pass 2 applied
+  if (nw > 0 && K.repel) walls_pass2_apply<double>(K, push, px, py, vx, vy);
+  // ---- propose (Agent.py:216), collisions, boundary safety net
+  propose_step<double>(vx, vy, dt, px, py);
+  handle_collisions<double>(K, s_w, near.x2min, ppx, ppy, px, py, vx, vy, n_bounce, n_sat);
+  boundary_net<double>(K, a, s_w, 0, b, aid, px, py, n_bc, n_sat);
+  // ---- the output-only tail (Agent.py:456-507)
+  double dpx, dpy;
+  step_displacement<double>(a, px, py, ppx, ppy, dpx, dpy);
+  StepTail<double> tl{mvx, mvy, mrot, hx, hy, dist, n_still};
+  tl = step_tail<double>(tl, dpx, dpy, tail_c, a.step0, aid, a.k0, a.k1);
+  mvx = tl.mvx; mvy = tl.mvy; mrot = tl.mrot; hx = tl.hx; hy = tl.hy; dist = tl.dist; n_still = tl.n_still;
+}
+
+// (replica writer, helper waves) their share of the lanes' books while the movers move: the reward cache's update ...
+__device__ __forceinline__ void s1_helper_rewards(const Step1Task& tk, const lds_f64_ptr goals, const int64_t b, const int tid,
+                                                  const RewardsIn& trin, int* s_rw_n, double* s_rw_total) {
+  RIAB_EXACT_FP
+  const RewardsOut ro = rewards_step(tk.a, goals, b, trin);
+  s_rw_n[tid & 255] = ro.n_rw;
+  s_rw_total[tid & 255] = ro.total;
+}
+// ... and what a reset of the lane would draw (position, next episode's goals)
+template <class XY, class List>
+__device__ __forceinline__ void s1_helper_draws(const Step1Task& tk, const ResetArgs& tr, const int64_t b, const int tid, XY& s_draw_xy,
+                                                List& s_draw_list) {
+  RIAB_EXACT_FP
+  const ResetDraw d = reset_draw(tk.a, tr, b);
+  s_draw_xy[0][tid & 255] = d.x;
+  s_draw_xy[1][tid & 255] = d.y;
+  s_draw_list[0][tid & 255] = (unsigned long long)d.list;
+  s_draw_list[1][tid & 255] = (unsigned long long)(d.list >> 64);
+}
+
+// (one world, the writer with the last ticket, thread 0) the world's reset, and whether the agents are to follow it
+__device__ __forceinline__ void s1_world_reset(const Step1Task& tk, const bool reset, WorldShared& s_world) {
+  RIAB_EXACT_FP
+  if (reset) {  // GoalCache.reset (:1218-1252): one selection — the shared list —, the world's episode table
+    const ResetDraw d = reset_draw_id(tk.a, tk.r, RIAB_WORLD_STREAM_ID);
+    Lane nl;
+    nl.list = d.list;
+    nl.n_goals = tk.r.n_select < tk.a.n_pool ? tk.r.n_select : tk.a.n_pool;
+    world_reset_books(tk.a, tk.r, tk.world, tk.t_env, nl, tk.diag);
+    for (int i = 0; i < RIAB_TASK_MAX_GOALS; ++i) s_world.list[i] = (uint8_t)list_get(nl.list, i);
+    s_world.n = nl.n_goals;
+  }
+  s_world.next_agent = reset ? 1 : 0;
+}
+
+// save_to_history (Agent.py:514-520)
+__device__ __forceinline__ void s1_store_history(float* const hist, const int64_t b, const int64_t B, const double px, const double py,
+                                                 const double mvx, const double mvy, const double hx, const double hy, const double mrot,
+                                                 const double dist) {
+  float* h = hist + b;
+  h[0 * B] = (float)px;
+  h[1 * B] = (float)py;
+  h[2 * B] = (float)mvx;
+  h[3 * B] = (float)mvy;
+  h[4 * B] = (float)hx;
+  h[5 * B] = (float)hy;
+  h[6 * B] = (float)mrot;
+  h[7 * B] = (float)dist;
+}
+
+// a wave's share of the cell groups: groups g0 .. g0 + reps - 1, the first one population pi0's; `mine`: the first
+// group's parameters where they stay in a register (no task)
+struct S1Share {
+  int wave, lane, g0, pi0, reps;
+  float mine;
+};
+typedef float S1Row[4][256];                            // x, y, head direction x, y of the segment's agents
+typedef float S1Par[RIAB_S1_WAVES][RIAB_S1_STAGE][64];  // each wave's cell groups' parameters, one per lane and group
+
+// ---- Neurons.update of the population: this wave's cell groups for the segment's 256 agents ----------------------
+// (`store`: the lanes that write their quad's values — all of them, but for the pass that follows a reset; `pick`: the
+// lambda of step1_body that fetches a population's record)
+template <int SPK, bool NT, int TASK, int KIND, class Pick>
+__device__ __forceinline__ void s1_rates_pass(const Step1Pops& ps, const Pick& pick, const S1Share& w, const S1Row& s_row,
+                                              const S1Par& s_par, const int64_t B, const v4f rx, const v4f ry, const bool store) {
+  constexpr bool MULTI = KIND < 0, MINE_REG = TASK == 0;
+  const int lane = w.lane, wave = w.wave;
+  v4f rhx = {0.0f, 0.0f, 0.0f, 0.0f}, rhy = rhx;
+  if (ps.needs_hd) {
+    rhx = *reinterpret_cast<const v4f*>(&s_row[2][4 * lane]);
+    rhy = *reinterpret_cast<const v4f*>(&s_row[3][4 * lane]);
+  }
+  const uint32_t quad = blockIdx.x * 64u + (uint32_t)lane;  // the lane's quad of agents within the row
+  float params = MINE_REG ? w.mine : s_par[wave][0][lane];
+  int pi = w.pi0;
+  Step1Pop q = pick(pi);
+  for (int r = 0; r < w.reps; ++r) {
+    const int g = w.g0 + r;
+    if (g >= ps.total_groups) break;  // wave-uniform
+    const float cur = params;
+    if (r + 1 < w.reps) params = s_par[wave][r + 1][lane];  // (asked for before this group's stores are issued)
+    if (MULTI && g >= q.group0 + q.n_groups && pi + 1 < ps.n_pops) q = pick(++pi);
+    s1_group_any<SPK, NT, TASK != 0, KIND>(ps, q, g - q.group0, cur, rx, ry, rhx, rhy, B, quad, store);
+  }
+}
+// ---- (one world, rate workgroups) did the world's episode end?  Then every agent was teleported (where to is a function
+// of (seed, counter, agent) alone: this lane's quad works it out for itself) and the wave runs its pass again on the new
+// row.  `world_verdict`: the lambda of step1_body that polls for it
+template <int SPK, bool NT, int TASK, int KIND, class Pick, class Verdict>
+__device__ __forceinline__ void s1_world_second_pass(const Step1Pops& ps, const Step1Sync& sy, const Step1Task& tk, const Pick& pick,
+                                                     const Verdict& world_verdict, const S1Share& w, const S1Row& s_row,
+                                                     const S1Par& s_par, const int64_t B) {
+  RIAB_EXACT_FP
+  const int lane = w.lane;
+  bool stale;
+  const unsigned long long e = world_verdict(stale);
+  const uint32_t flags = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)e, 0);
+  if (stale) {
+    if (lane == 0) step1_note_timeout(sy, ps.step0);
+  } else if ((flags & 1u) && tk.r.teleport) {
+    v4f rx = *reinterpret_cast<const v4f*>(&s_row[0][4 * lane]), ry = *reinterpret_cast<const v4f*>(&s_row[1][4 * lane]);
+    const int64_t b4 = (int64_t)blockIdx.x * 256 + 4 * lane;
+    float nx[4], ny[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const ResetDraw d = reset_draw_id(tk.a, tk.r, (uint64_t)(tk.r.agent_id0 + b4 + k));
+      nx[k] = (float)d.x;
+      ny[k] = (float)d.y;
+    }
+    const bool l0 = b4 + 0 < tk.a.B, l1 = b4 + 1 < tk.a.B, l2 = b4 + 2 < tk.a.B, l3 = b4 + 3 < tk.a.B;  // (lanes of the task)
+    rx.x = l0 ? nx[0] : rx.x; ry.x = l0 ? ny[0] : ry.x;
+    rx.y = l1 ? nx[1] : rx.y; ry.y = l1 ? ny[1] : ry.y;
+    rx.z = l2 ? nx[2] : rx.z; ry.z = l2 ? ny[2] : ry.z;
+    rx.w = l3 ? nx[3] : rx.w; ry.w = l3 ? ny[3] : ry.w;
+    drain_stores();  // (the values this wave stored a moment ago are in place)
+    s1_rates_pass<SPK, NT, TASK, KIND>(ps, pick, w, s_row, s_par, B, rx, ry, true);
+  }
+}
+
+// ---- the schedule ---------------------------------------------------------------------------------------------------
+// A workgroup's eight waves take different branches and must meet at the same barriers.  Who takes which, in program
+// order ("all": the role's waves take it in every instantiation; a condition: only where the template bits say so; "-":
+// never.  RT / WT: the task bits of a replica / one-world task, as step1_body derives them):
+//
+//                                    1        2        3        4        5, 6     7, 8      9        10
+//                                    tables   normals  rewards  draws    ticket   verdict   lists    row
+//                                    staged   in LDS   ready    ready                       ready    in LDS
+//   kind                             sync     sync     lds      lds      sync     sync      lds      sync
+//   plain workgroup (no task)        all      all      -        -        -        -         -        all
+//   task rate workgroup (y >= 1)     all      all      -        -        -        -         -        all
+//   replica writer, movers (0-3)     all      all      RT       RT       -        -         RT & 4   -
+//   replica writer, helpers (4-7)    all      all      RT       RT       -        -         RT & 4   -
+//   one-world writer, all 8 waves    all      all      -        -        WT       WT (*)    -        -
+//
+//   sync: __syncthreads().  lds: lds_barrier() under its name — s1_sync_rewards_ready(), s1_sync_draws_ready(),
+//   s1_sync_lists_ready() —, called once by the producer and once by the consumer: the helpers in `if (RT && writer &&
+//   !mover)` (3, 4) and in `else if ((RT & 4) && writer)` (9), the movers in `else if (RT && writer && mover)` (3, 4, 9).
+//   (*) only in the ONE writer workgroup of the grid that took the last ticket (s_world.last, workgroup-uniform); between 6
+//   and 7 that workgroup's eight waves call world_phase_b, which has barriers of its own.
+//   10 is skipped by a task's writer as a whole workgroup (TASK && writer): its movers go on to the write-back while its
+//   helpers are still busy with the next action.
 template <int SPK, bool NT, int TASK, int KIND>
 __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& ps, const Step1Sync& sy,
                                            const int reps, const MotionConst<double>& hk, const TailConst<double>& tail_c,
@@ -391,13 +653,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     if (tlive) tin = task_lane_load<RT>(tk.a, b);
     if (hlive && (RT & 1)) trin = load_rewards_in(tk.a, b);
     if (writer) task_stage_goals(tk.a, s_goals, tid, NT_);
-    if (WT && writer) {  // the world's list as this step finds it, the lane's reward rows: one batch with the state
-      if (tid < RIAB_TASK_MAX_GOALS) s_world.list[tid] = (uint8_t)((int)tk.world[RIAB_TW_GOAL_LIST + tid] & 0xFF);
-      if (tid == 0) s_world.n = (int)tk.world[RIAB_TW_N_GOALS];
-      w_pad_start0 = tk.world[RIAB_TW_PAD_START];
-      w_terminal_prev = tk.world[RIAB_TW_TERMINAL] != 0.0 ? 1 : 0;
-      if (wlive) win = world_lane_load(tk.a, b);
-    }
+    if (WT && writer) s1_world_prefetch(tk, b, tid, wlive, s_world, win, w_pad_start0, w_terminal_prev);
   }
   // (the box fast path's verdict, worked out once per plan by walls_prepare_kernel)
   const uint32_t box_word = *reinterpret_cast<const uint32_t*>(sy.walls + RIAB_MAX_WALLS);
@@ -467,7 +723,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
   for (int i = tid; i < a.n_walls * (int)(sizeof(Wall<double>) / sizeof(double)); i += NT_)
     reinterpret_cast<double*>(s_w)[i] = reinterpret_cast<const double*>(sy.walls)[i];
   stage_wall_grid(a, s_grid, tid, NT_);
-  __syncthreads();
+  __syncthreads();  // the tables are in LDS
 #ifdef RIAB_STEP1_PROFILE
   if (prof_slot >= 0) {  // (the state must have arrived: its first use would otherwise be timed with the motion step)
     drain_stores();
@@ -491,10 +747,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
   double ispeed = 0, nv64 = 0, ppx = 0, ppy = 0;
   bool zero_v = false;
   if (!mover) {
-    u32x4 pw = {0u, 0u, 0u, 0u};
-    const MotionDraw d = motion_normals(a.step0, true, aid, a.k0, a.k1, pw);
-    s_z[0][tid & 255] = d.z_rot;
-    s_z[1][tid & 255] = d.z_spd;
+    s1_draw_normals(a, aid, tid, s_z);
   } else {
     const lds_cf64_ptr lds_g = (lds_cf64_ptr)s_g;
 #pragma unroll
@@ -530,63 +783,15 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
   tr.pos_x = tr.pos_y = nullptr;
   tr.hist_x = tr.hist_y = nullptr;
   if (RT && writer && !mover) {  // (wave-uniform) the helper waves' share of the lanes' books, see above
-    if (hlive && (RT & 1)) {
-      const RewardsOut ro = rewards_step(tk.a, (lds_f64_ptr)s_goals, b, trin);
-      s_rw_n[tid & 255] = ro.n_rw;
-      s_rw_total[tid & 255] = ro.total;
-    }
-    lds_barrier();  // (writer) the reward caches are up to date
-    if (hlive && (RT & 2)) {
-      const ResetDraw d = reset_draw(tk.a, tr, b);
-      s_draw_xy[0][tid & 255] = d.x;
-      s_draw_xy[1][tid & 255] = d.y;
-      s_draw_list[0][tid & 255] = (unsigned long long)d.list;
-      s_draw_list[1][tid & 255] = (unsigned long long)(d.list >> 64);
-    }
-    lds_barrier();  // (writer) the resets' draws are in LDS
+    if (hlive && (RT & 1)) s1_helper_rewards(tk, (lds_f64_ptr)s_goals, b, tid, trin, s_rw_n, s_rw_total);
+    s1_sync_rewards_ready();
+    if (hlive && (RT & 2)) s1_helper_draws(tk, tr, b, tid, s_draw_xy, s_draw_list);
+    s1_sync_draws_ready();
     RIAB_S1_STAMP_H(14)
   }
-  if (mover) {
-    const lds_cf64_ptr lds_h = (lds_cf64_ptr)s_h;
-    const double z_rot = (double)s_z[0][tid], z_spd = (double)s_z[1][tid];
-    rot = ou_step<double>(rot, m.rot_theta_kw, m.rot_drift_kw, m.rot_sigma_kw, dt, z_rot);
-    {
-      double sn, cs;
-      sincos_small(rot * dt, &sn, &cs);
-      rotate_by<double>(cs, sn, vx, vy);
-      vx = zero_v ? 1e-8 : vx;
-      vy = zero_v ? 0.0 : vy;
-    }
-    // the speed's OU step in normal space and normal_to_rayleigh (utils.py:409-413)
-    nv64 = ou_step<double>(nv64, m.speed_theta_kw, 0.0, m.speed_sigma_kw, m.dt, z_spd);
-    const bool h_in_table = fabs(nv64) < RIAB_H_NMAX;
-    const SegRow<RIAB_H_DEG> hrow = seg_fetch<RIAB_H_DEG>(lds_h + seg_H(nv64) * RIAB_H_STRIDE);
-    double speed_new;
-    {
-      const double tnew = h_in_table ? seg_eval<RIAB_H_DEG>(hrow, nv64) : sqrt(-2.0 * log(1.0 - normcdf(nv64)));
-      speed_new = m.speed_mean_kw * tnew;
-    }
-    if (m.speed_std_is_zero) speed_new = K.sm_kw;
-    {
-      const double f = speed_new * ispeed;
-      vx *= f;
-      vy *= f;
-    }
-    // ---- _drift_velocity_update (Agent.py:331-341)
-    if (m.has_drift) drift_update<double>(m.drift_theta, drx, dry, dt, vx, vy);
-    // ---- _wall_velocity_update, pass 2 applied
-    if (nw > 0 && K.repel) walls_pass2_apply<double>(K, push, px, py, vx, vy);
-    // ---- propose (Agent.py:216), collisions, boundary safety net
-    propose_step<double>(vx, vy, dt, px, py);
-    handle_collisions<double>(K, s_w, near.x2min, ppx, ppy, px, py, vx, vy, n_bounce, n_sat);
-    boundary_net<double>(K, a, s_w, 0, b, aid, px, py, n_bc, n_sat);
-    // ---- the output-only tail (Agent.py:456-507)
-    double dpx, dpy;
-    step_displacement<double>(a, px, py, ppx, ppy, dpx, dpy);
-    StepTail<double> tl{mvx, mvy, mrot, hx, hy, dist, n_still};
-    tl = step_tail<double>(tl, dpx, dpy, tail_c, a.step0, aid, a.k0, a.k1);
-    mvx = tl.mvx; mvy = tl.mvy; mrot = tl.mrot; hx = tl.hx; hy = tl.hy; dist = tl.dist; n_still = tl.n_still;
-  }
+  if (mover)
+    s1_motion_back(a, tail_c, K, s_w, s_h, s_z, near, push, ispeed, nv64, ppx, ppy, zero_v, drx, dry, b, aid, tid, px, py, vx, vy, rot, mvx,
+                   mvy, mrot, hx, hy, dist, n_bounce, n_sat, n_bc, n_still);
   RIAB_S1_STAMP(2)
   // ---- the writer's part: the state in place, once nobody can read the old one any more.  Each of its mover waves asks
   // for its segment's arrival words BEFORE its share of the rates (task: before its lanes' bookkeeping) — the request
@@ -659,19 +864,8 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
                                                     tk.reward_out, tk.terminal_out, tk.met, tk.cand, tk.ctl, tk.diag);
       const bool reset = (WT & 2) && terminal_last;
       __syncthreads();
-      if (tid == 0) {
-        if (reset) {  // GoalCache.reset (:1218-1252): one selection — the shared list —, the world's episode table
-          const ResetDraw d = reset_draw_id(tk.a, tk.r, RIAB_WORLD_STREAM_ID);
-          Lane nl;
-          nl.list = d.list;
-          nl.n_goals = tk.r.n_select < tk.a.n_pool ? tk.r.n_select : tk.a.n_pool;
-          world_reset_books(tk.a, tk.r, tk.world, tk.t_env, nl, tk.diag);
-          for (int i = 0; i < RIAB_TASK_MAX_GOALS; ++i) s_world.list[i] = (uint8_t)list_get(nl.list, i);
-          s_world.n = nl.n_goals;
-        }
-        s_world.next_agent = reset ? 1 : 0;
-      }
-      __syncthreads();
+      if (tid == 0) s1_world_reset(tk, reset, s_world);
+      __syncthreads();  // the list the next step finds is in LDS
       if (tid < 5) {
         uint32_t v;
         if (tid == 0) v = (uint32_t)s_world.next_agent | ((uint32_t)s_world.n << 8);
@@ -724,7 +918,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
 #else
     const NoProbe probe;
 #endif
-    lds_barrier();  // (writer) the reward caches are up to date: the helper waves' rewards_step
+    s1_sync_rewards_ready();
     // (the arrival words are taken delivery of HERE, before the bookkeeping's first store: the wait counter is one for
     // loads and stores, and the compiler — which must assume the worst at every join of this branchy code — otherwise
     // drains the bookkeeping's stores, the write-through mail included, in the middle of the chain to keep that one
@@ -734,16 +928,15 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
       const RewardsOut ro = {s_rw_n[tid], s_rw_total[tid]};
       tmid = task_lane_goals<RT>(tk.a, b, (lds_f64_ptr)s_goals, tin, ro, qx, qy, tk.t_env, tk.reward_out, tk.terminal_out, tk.diag, probe);
     }
-    lds_barrier();  // (writer) the resets' draws are in LDS
+    s1_sync_draws_ready();
     if (tlive)
       task_lane_reset<RT>(tk.a, tr, b, tin, tmid, qx, qy, tk.t_env, tk.diag, [&]() {
         return ResetDraw{s_draw_xy[0][tid], s_draw_xy[1][tid], ((u128)s_draw_list[1][tid] << 64) | (u128)s_draw_list[0][tid]};
       });
     const bool moved = tlive && !(qx == mx && qy == my);  // (a reset that teleported the lane)
-    uint32_t* const mail = tk.mail + (int64_t)blockIdx.x * RIAB_STEP1_MAIL_STRIDE;
     // who moved and where to: 8-byte entries that carry the epoch themselves (epoch << 32 | value), so that none of them
     // has to be ordered against another — or against the bookkeeping's stores and the episode table's atomic, which are
-    // still in flight.  This wave's two verdict entries (the halves of its lane mask) are posted every step.
+    // still in flight.  (In a function of its own, by value, this posting changes the replica kernels' code.)
     const unsigned long long lanes = __builtin_amdgcn_ballot_w64(moved);
     uint64_t* const mail64 = reinterpret_cast<uint64_t*>(tk.mail + (int64_t)blockIdx.x * RIAB_STEP1_MAIL_STRIDE);
     // this wave's six verdict entries, posted every step: the halves of its mask of moved lanes and — what the others
@@ -777,7 +970,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
       }
     }
     RIAB_S1_STAMP(13)
-    if (RT & 4) lds_barrier();  // (writer) the lanes' lists and positions are in LDS
+    if (RT & 4) s1_sync_lists_ready();
     if (tlive) {
       task_lane_store<RT>(tk.a, b, tin, tmid);
       px = qx;
@@ -788,7 +981,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
     // ---- the helper waves' last share: the coming step's action of every lane (get_goal_vector, :1555-1584), into the
     // drift buffer — which every workgroup of the segment read at the top: behind the arrival words, like the state
     uint32_t hseen = arrivals();
-    lds_barrier();  // (writer) the lanes' lists and positions are in LDS
+    s1_sync_lists_ready();
     double hx_ = 0.0, hy_ = 0.0;
     if (hlive) {
       Lane hl = {};
@@ -798,6 +991,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
       hl.py = s_draw_xy[1][tid & 255];
       goal_vector(tk.a, (lds_f64_ptr)s_goals, hl, tk.gv_scale, hx_, hy_);
     }
+    // (the movers' wait_arrivals on this wave's own word: called from here, the lambda compiles to another loop in both places)
     bool late = false;
     for (uint32_t spins = 0; __builtin_amdgcn_ballot_w64(hseen != sy.epoch) != 0; ++spins) {
       if (spins >= sy.spin_limit) {
@@ -821,33 +1015,12 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
       s_row[3][tid] = (float)hy;
     }
   }
-  if (mover && writer && !TASK && a.hist) {  // save_to_history (Agent.py:514-520)
-    float* h = a.hist + b;
-    h[0 * B] = (float)px;
-    h[1 * B] = (float)py;
-    h[2 * B] = (float)mvx;
-    h[3 * B] = (float)mvy;
-    h[4 * B] = (float)hx;
-    h[5 * B] = (float)hy;
-    h[6 * B] = (float)mrot;
-    h[7 * B] = (float)dist;
-  }
+  if (mover && writer && !TASK && a.hist) s1_store_history(a.hist, b, B, px, py, mvx, mvy, hx, hy, mrot, dist);
   // the row is in LDS; every state value of this workgroup has been consumed, i.e. loaded.  (A task's writer writes no
   // rates: its movers go on to the write-back while its helper waves are still busy with the next action.)
   if (!(TASK && writer)) __syncthreads();
-  if (TASK && writer && mover) {  // (the lanes' books are kept: a reset may have moved them)
-    if (a.hist) {  // save_to_history (Agent.py:514-520), agent.history["pos"][-1] = agent.pos of a teleporting reset included
-      float* h = a.hist + b;
-      h[0 * B] = (float)px;
-      h[1 * B] = (float)py;
-      h[2 * B] = (float)mvx;
-      h[3 * B] = (float)mvy;
-      h[4 * B] = (float)hx;
-      h[5 * B] = (float)hy;
-      h[6 * B] = (float)mrot;
-      h[7 * B] = (float)dist;
-    }
-  }
+  // (a task's writer keeps the lanes' books: agent.history["pos"][-1] = agent.pos of a teleporting reset included)
+  if (TASK && writer && mover && a.hist) s1_store_history(a.hist, b, B, px, py, mvx, mvy, hx, hy, mrot, dist);
   if (!writer && tid == 0)
     st_agent(sy.words + (int64_t)blockIdx.x * RIAB_STEP1_SYNC_STRIDE + blockIdx.y, sy.epoch);
 
@@ -855,49 +1028,31 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
   auto write_back = [&]() {
     wait_arrivals();
     RIAB_S1_STAMP(5)
-    {
-      st[0 * B] = px;
-      st[1 * B] = py;
-      st[2 * B] = vx;
-      st[3 * B] = vy;
-      st[4 * B] = rot;
-      st[5 * B] = mvx;
-      st[6 * B] = mvy;
-      st[7 * B] = mrot;
-      st[8 * B] = hx;
-      st[9 * B] = hy;
-      st[10 * B] = dist;
-      st[11 * B] = dwall;
-      if (a.diag) {
-        if (n_bounce) atomicAdd(a.diag + 0, n_bounce);
-        if (n_sat) atomicAdd(a.diag + 1, n_sat);
-        if (n_bc) atomicAdd(a.diag + 2, n_bc);
-        if (n_still) atomicAdd(a.diag + 3, n_still);
-      }
-    }
+    s1_store_state(a, st, px, py, vx, vy, rot, mvx, mvy, mrot, hx, hy, dist, dwall, n_bounce, n_sat, n_bc, n_still);
   };
 
-  // ---- Neurons.update of the population: this wave's cell groups for the segment's 256 agents ----------------------
-  // (`store`: the lanes that write their quad's values — all of them, but for the pass that follows a reset, below)
-  auto rates_pass = [&](const v4f rx, const v4f ry, const bool store) __attribute__((always_inline)) {
-    v4f rhx = {0.0f, 0.0f, 0.0f, 0.0f}, rhy = rhx;
-    if (ps.needs_hd) {
-      rhx = *reinterpret_cast<const v4f*>(&s_row[2][4 * lane]);
-      rhy = *reinterpret_cast<const v4f*>(&s_row[3][4 * lane]);
-    }
-    const uint32_t quad = blockIdx.x * 64u + (uint32_t)lane;  // the lane's quad of agents within the row
-    float params = MINE_REG ? mine : s_par[wave][0][lane];
-    int pi = pi0;
-    Step1Pop q = pick(pi);
-    for (int r = 0; r < reps; ++r) {
-      const int g = g0 + r;
-      if (g >= ps.total_groups) break;  // wave-uniform
-      const float cur = params;
-      if (r + 1 < reps) params = s_par[wave][r + 1][lane];  // (asked for before this group's stores are issued)
-      if (MULTI && g >= q.group0 + q.n_groups && pi + 1 < ps.n_pops) q = pick(++pi);
-      s1_group_any<SPK, NT, TASK != 0, KIND>(ps, q, g - q.group0, cur, rx, ry, rhx, rhy, B, quad, store);
-    }
-  };
+  // ---- Neurons.update: this wave's cell groups; a task's rate workgroups again where a reset moved an agent
+  const S1Share share = {wave, lane, g0, pi0, reps, mine};
+  if (rates_here)
+    s1_rates_pass<SPK, NT, TASK, KIND>(ps, pick, share, s_row, s_par, B, *reinterpret_cast<const v4f*>(&s_row[0][4 * lane]),
+                                       *reinterpret_cast<const v4f*>(&s_row[1][4 * lane]), true);
+  RIAB_S1_STAMP(3)
+#ifdef RIAB_STEP1_PROFILE
+  if (prof_slot >= 0) {
+    drain_stores();
+    RIAB_S1_STAMP(4)
+  }
+#endif
+  // (a wave whose groups are all HeadDirectionCells' writes nothing a reset can change: no wait at all)
+  bool wave_needs_pos = false;
+  if (TASK && !writer) {
+#pragma unroll
+    for (int k = 0; k < (MULTI ? RIAB_STEP1_MAX_POPS : 1); ++k)  // (a population other than HeadDirectionCells with a group in this wave's range)
+      wave_needs_pos = wave_needs_pos || (k < ps.n_pops && ps.pop[k].kind != S1_KIND_HDC && ps.pop[k].group0 < g0 + reps &&
+                                          ps.pop[k].group0 + ps.pop[k].n_groups > g0);
+  }
+  if (WT && (WT & 2) && !writer && wave_needs_pos)
+    s1_world_second_pass<SPK, NT, TASK, KIND>(ps, sy, tk, pick, world_verdict, share, s_row, s_par, B);
   // (a task's step) this wave's cell groups again, for the quads `mq` of the segment alone (s1_group_few) — whose new
   // positions the lanes that hold them (`moved`) put into the row in LDS first: every wave of the workgroup writes the
   // same values there, and reads what it wrote itself
@@ -919,50 +1074,6 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
                                                    (lds_cf32_ptr)&s_row[0][0]);
     }
   };
-  if (rates_here)
-    rates_pass(*reinterpret_cast<const v4f*>(&s_row[0][4 * lane]), *reinterpret_cast<const v4f*>(&s_row[1][4 * lane]), true);
-  RIAB_S1_STAMP(3)
-#ifdef RIAB_STEP1_PROFILE
-  if (prof_slot >= 0) {
-    drain_stores();
-    RIAB_S1_STAMP(4)
-  }
-#endif
-  // (a wave whose groups are all HeadDirectionCells' writes nothing a reset can change: no wait at all)
-  bool wave_needs_pos = false;
-  if (TASK && !writer) {
-#pragma unroll
-    for (int k = 0; k < (MULTI ? RIAB_STEP1_MAX_POPS : 1); ++k)  // (a population other than HeadDirectionCells with a group in this wave's range)
-      wave_needs_pos = wave_needs_pos || (k < ps.n_pops && ps.pop[k].kind != S1_KIND_HDC && ps.pop[k].group0 < g0 + reps &&
-                                          ps.pop[k].group0 + ps.pop[k].n_groups > g0);
-  }
-  if (WT && (WT & 2) && !writer && wave_needs_pos) {
-    // ---- did the world's episode end?  Then every agent was teleported (where to is a function of (seed, counter,
-    // agent) alone: this lane's quad works it out for itself) and the wave runs its pass again on the new row
-    bool stale;
-    const unsigned long long e = world_verdict(stale);
-    const uint32_t flags = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)e, 0);
-    if (stale) {
-      if (lane == 0) step1_note_timeout(sy, ps.step0);
-    } else if ((flags & 1u) && tk.r.teleport) {
-      v4f rx = *reinterpret_cast<const v4f*>(&s_row[0][4 * lane]), ry = *reinterpret_cast<const v4f*>(&s_row[1][4 * lane]);
-      const int64_t b4 = (int64_t)blockIdx.x * 256 + 4 * lane;
-      float nx[4], ny[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const ResetDraw d = reset_draw_id(tk.a, tk.r, (uint64_t)(tk.r.agent_id0 + b4 + k));
-        nx[k] = (float)d.x;
-        ny[k] = (float)d.y;
-      }
-      const bool l0 = b4 + 0 < tk.a.B, l1 = b4 + 1 < tk.a.B, l2 = b4 + 2 < tk.a.B, l3 = b4 + 3 < tk.a.B;  // (lanes of the task)
-      rx.x = l0 ? nx[0] : rx.x; ry.x = l0 ? ny[0] : ry.x;
-      rx.y = l1 ? nx[1] : rx.y; ry.y = l1 ? ny[1] : ry.y;
-      rx.z = l2 ? nx[2] : rx.z; ry.z = l2 ? ny[2] : ry.z;
-      rx.w = l3 ? nx[3] : rx.w; ry.w = l3 ? ny[3] : ry.w;
-      drain_stores();  // (the values this wave stored a moment ago are in place)
-      rates_pass(rx, ry, true);
-    }
-  }
   if (RT && !writer && wave_needs_pos) {
     // ---- did a reset move one of the segment's agents?  The writer's 4 x 6 verdict entries of this launch: one round
     // trip (they are usually there by now) says that they are posted, which agents moved and where (almost all of) them went.
@@ -1054,7 +1165,7 @@ __device__ __forceinline__ void step1_body(const AgentArgs& a, const Step1Pops& 
       // the tail of the step's critical path)
       drain_stores();  // (the values this wave stored for those quads a moment ago are in place)
       if (RIAB_S1_FEW) rates_few(rx, ry, mine_moved);
-      else rates_pass(rx, ry, mine_moved);
+      else s1_rates_pass<SPK, NT, TASK, KIND>(ps, pick, share, s_row, s_par, B, rx, ry, mine_moved);
     }
     RIAB_S1_STAMP(12)
     if (stale && lane == 0) step1_note_timeout(sy, ps.step0);

@@ -12,7 +12,7 @@ LLVM_BIN = "/opt/rocm/llvm/bin"
 RET_ADD = re.compile(r"^(global|flat)_atomic_add(_u32)?\s.*\bsc0\b")  # a returning atomic add
 STORE = re.compile(r"^(global|flat|scratch|buffer)_(store|atomic)")
 TERMINAL = re.compile(r"^global_store_byte\s.*\bsc1\b")  # phase A's last write-through store: the `terminal` column
-# Every kernel with a stack frame, and its size in bytes.  The two step1 instantiations are the ones launch_step1_cell
+# Every kernel with a stack frame, and its size in bytes.  The two step1 instantiations are the ones launch_step1_impl
 # refuses (a frame needs scratch set up per dispatch); the float64 helper-wave motion kernels carry a
 # small one.  A kernel that gains a frame, or a frame that grows, fails here.
 FRAMES = {"_ZN4riab17step1_task_kernelILi1ELi11ELin1EEE": 352, "_ZN4riab17step1_task_kernelILi1ELi15ELin1EEE": 352,

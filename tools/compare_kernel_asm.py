@@ -5,7 +5,10 @@
 
 Compiles ratinabox_amd/csrc/<TU> of both trees to device assembly with the flags of ratinabox_amd/_build.py (plus any
 extra flags given), cuts the two texts into functions and prints the symbols that exist in one tree only and those
-whose text differs, with the size of the difference.  Exit status 0: the same symbols, the same text for each.
+whose text is not identical, with the size of the difference and a verdict: `permuted` — the same instructions up to
+their order and the numbers of their registers, everything else (kernel descriptor, resource comments, labels) the same
+text, see classify() — or `differs`.  Exit status 0: the same symbols, the same text for each; 3: the same symbols, each
+identical or permuted; 1: a symbol differs or is missing; 2: usage, or a compilation failed.
 
 Plain text comparison: a function's text is everything between the assembler's "Begin function" / "End function"
 comments — instructions, the kernel descriptor, the resource summary.  Three things are taken out first: the padding
@@ -30,6 +33,9 @@ _spec.loader.exec_module(_build)
 BEGIN = re.compile(r"-- Begin function (\S+)")
 PAD = re.compile(r"[ \t]+;")
 LOCAL = re.compile(r"(\.L|\b)(BB|func_begin|func_end|tmp)\d+")
+INSTRUCTION = re.compile(r"\s+([a-z][a-z0-9_]*\b|;\s*(implicit-def|kill):)")  # (directives start with a dot, labels in column 0)
+REG = re.compile(r"\b([vsa])(?:\d+\b|(\[)\d+:\d+\])")
+NOTE_REG = re.compile(r"\$([vsa])gpr\d+(?:_[vsa]gpr\d+)*")
 
 
 def assemble(tree, tu, extra, out):
@@ -57,6 +63,32 @@ def functions(path):
     return out
 
 
+def _is_instruction(line):
+    """An instruction, or the allocator's note on a register in front of one (`; implicit-def: $vgpr18`, `; kill: ...`)."""
+    return bool(INSTRUCTION.match(line))
+
+
+def _mask(line):
+    return NOTE_REG.sub(lambda m: m.group(1) + "gpr#", REG.sub(lambda m: m.group(1) + ("[#]" if m.group(2) else "#"), line))
+
+
+def classify(old, new):
+    """'identical', 'permuted' or 'differs' for two functions' lines (as functions() returns them).
+
+    permuted: the same instructions up to their order and the numbers of their registers — everything that is not an
+    instruction (labels, directives, the .amdhsa_ kernel descriptor, the resource comments: register counts, scratch and
+    LDS size, code length, occupancy) is the same text in the same order, and the instruction lines are the same
+    multiset once v12, s[4:5], a3, v[6:7] read v#, s[#], a#, v[#].  An opcode, an immediate, a label or a wait count
+    that changed is 'differs'."""
+    if old == new:
+        return "identical"
+    if [l for l in old if not _is_instruction(l)] != [l for l in new if not _is_instruction(l)]:
+        return "differs"
+    if sorted(_mask(l) for l in old if _is_instruction(l)) != sorted(_mask(l) for l in new if _is_instruction(l)):
+        return "differs"
+    return "permuted"
+
+
 def main(argv):
     tmp = None
     if len(argv) == 2 and all(a.endswith(".s") for a in argv):
@@ -77,17 +109,19 @@ def main(argv):
     old, new = functions(old_s), functions(new_s)
     if tmp:
         shutil.rmtree(tmp, ignore_errors=True)
-    bad = 0
+    bad = permuted = 0
     for sym in sorted(set(old) ^ set(new)):
         print(("only in old: " if sym in old else "only in new: ") + sym)
         bad += 1
     for sym in sorted(set(old) & set(new)):
-        if old[sym] != new[sym]:
+        verdict = classify(old[sym], new[sym])
+        if verdict != "identical":
             d = [l for l in difflib.unified_diff(old[sym], new[sym], n=0) if l[0] in "+-" and l[:3] not in ("+++", "---")]
-            print("differs (%d lines of %d): %s" % (len(d), len(old[sym]), sym))
-            bad += 1
-    print("%d functions in old, %d in new, %d differ or are missing" % (len(old), len(new), bad))
-    return 1 if bad else 0
+            print("%s (%d lines of %d): %s" % (verdict, len(d), len(old[sym]), sym))
+            permuted += verdict == "permuted"
+            bad += verdict == "differs"
+    print("%d functions in old, %d in new, %d permuted, %d differ or are missing" % (len(old), len(new), permuted, bad))
+    return 1 if bad else 3 if permuted else 0
 
 
 if __name__ == "__main__":
