@@ -1159,6 +1159,91 @@ int riab_theta_sequence_rollout(const RiabEnv* env, const RiabMotion* motion, co
 /* ShiftAgent (SubAgent.py:466-478): pos_out [2][B] = lead position + lead head direction * shift_m. */
 int riab_shift_agent_position(const double* lead_state, int64_t B, double shift_m, double* pos_out, riab_stream_t stream);
 
+/* diag of riab_dumb_agent_step: device int32 [4] or NULL, accumulated over the lanes b < n_agents */
+enum {
+  RIAB_DUMB_DIAG_WALL_CUTS = 0,    /* lane-steps whose spring crossed a wall and was shortened (SubAgent.py:169-173) */
+  RIAB_DUMB_DIAG_BOUNDARY = 1,     /* lane-steps whose position the boundary conditions changed (:177) */
+  RIAB_DUMB_DIAG_SATURATIONS = 2   /* ... of which the bounded rejection sampler (polygon / hole) ran out of attempts */
+};
+
+/* DumbAgent (SubAgent.py:118-179), one step: a wrong position on a spring round the lead.  Per lane, float64, every
+ * operation rounded on its own in the reference's order:
+ *   v += theta * (0 - v) * dt + sigma * (dt * z) + (-acceleration_scale * displacement * dt)       (:154-161)
+ *   displacement += v * dt                                                                           (:163)
+ *   the segment lead -> lead + displacement against every wall of env (utils.vector_intercepts, both line parameters
+ *   strictly inside (0, 1)): on a collision displacement *= 0.95 * the smallest fraction along the segment  (:167-173)
+ *   pos = Environment.apply_boundary_conditions(lead + displacement): periodic wrap, solid clamp, or — in a hole /
+ *   outside a polygon — the bounded rejection sampler of riab_agent_step keyed by (seed; step, agent id)       (:175-177)
+ *   displacement = pos - lead, wrapped by env->scale when periodic                                             (:178)
+ * theta = 1 / tau_v and sigma = sqrt(2 noise_scale^2 / (tau_v dt)) are prepared by the caller (utils.py:361-368).
+ * displacement, velocity: the lane state, device float64 [2][B] each, updated in place.  z_in: device float64 [2][B]
+ * standard normals or NULL => Philox keyed by (seed; step, agent_id0 + b) under a tag of its own, Box-Muller; z_out
+ * [2][B] or NULL records the normals used.  pos_out: device float64 [2][B].  B is the padded row length, lanes b >=
+ * n_agents are computed and not counted.  RIAB_EINVAL: null pointers, dt <= 0, n_agents outside 0..B; RIAB_EALIGN: B % 4;
+ * RIAB_ETOOBIG: more than RIAB_MAX_WALLS walls. */
+int riab_dumb_agent_step(const RiabEnv* env, const double* lead_state, int64_t B, int64_t n_agents, int64_t agent_id0,
+                         double* displacement, double* velocity, double dt, double theta, double sigma,
+                         double acceleration_scale, const double* z_in, double* z_out, uint64_t seed, uint64_t step,
+                         double* pos_out, int32_t* diag, riab_stream_t stream);
+
+/* ReplayAgent (SubAgent.py:358-432): the lead's position, except during "replays" — the lane detaches, explores from a
+ * random start at its replay speed, and snaps back.  The lane state besides the flag, device float64
+ * [RIAB_REPLAY_ROWS][B]: */
+enum {
+  RIAB_RP_SPEED = 0,    /* the replay's speed (a Rayleigh draw) */
+  RIAB_RP_T_START = 1,  /* replay_start_time */
+  RIAB_RP_T_END = 2,    /* replay_end_time */
+  RIAB_RP_D_START = 3,  /* the sham agent's distance travelled when the replay started */
+  RIAB_RP_LO = 4,       /* rows 4..6: the older record (distance since the start, x, y) */
+  RIAB_RP_HI = 7,       /* rows 7..9: the newer record */
+  RIAB_REPLAY_ROWS = 10
+};
+/* the outcomes of a lane's draws: device float64 [RIAB_REPLAY_DRAWS][B] */
+enum {
+  RIAB_RD_U = 0,          /* the trigger uniform (every lane outside a replay) */
+  RIAB_RD_SPEED = 1,      /* Rayleigh(replay_speed) */
+  RIAB_RD_DURATION = 2,   /* Rayleigh(replay_duration), before its floor of half the mean */
+  RIAB_RD_POS_X = 3,      /* the start: uniform in the environment */
+  RIAB_RD_POS_Y = 4,
+  RIAB_RD_DIRECTION = 5,  /* uniform in [0, 2 pi) */
+  RIAB_REPLAY_DRAWS = 6
+};
+/* diag: device int32 [4] or NULL, accumulated over the lanes b < n_agents */
+enum {
+  RIAB_REPLAY_DIAG_STARTED = 0,      /* replays started */
+  RIAB_REPLAY_DIAG_ENDED = 1,        /* replays ended */
+  RIAB_REPLAY_DIAG_SATURATIONS = 2,  /* lane-steps that needed more than K sham steps: the newest record is the position */
+  RIAB_REPLAY_DIAG_RESAMPLE = 3      /* start positions whose rejection sampler ran out of attempts */
+};
+
+/* One ReplayAgent.update() up to the forced step.  The reference simulates a replay's whole path (1.1 x speed x
+ * duration) into a table when it starts and interpolates the table afterwards; here a lane keeps the two records that
+ * bracket its query and its sham agent is advanced only as far as the query of this call needs — the same positions,
+ * since the query only grows.  `t`: the ReplayAgent's own clock when update() is entered.  Per lane:
+ *   outside a replay  u > freq_dt: the lead's position.  Otherwise a replay starts: speed, duration (floored at
+ *                     mean_duration / 2), start position and direction are drawn; POS, VEL (= speed_mean x the direction)
+ *                     and ROT_VEL (= 0) of sham_state are set; both records become (0, start); pos_out = the start.
+ *   in a replay, t < end   query = speed * (t - start time).  The sham agent is advanced by the motion model of
+ *                     riab_agent_step (`motion`, the same device code: a step has the bits of a riab_agent_step(T = 1)
+ *                     step on the same operands and the same wave) while its newest record lies below the query, at
+ *                     most K steps per call; pos_out = scipy's linear interp1d between the two records.  A wave leaves
+ *                     the loop when none of its lanes needs another step; lanes that do not keep stepping with their
+ *                     wave, and their state as it was is what is kept.  A lane out of steps takes its newest record.
+ *   in a replay, t >= end  the replay ends: the lead's position.
+ * flag: device int32 [B], 1 in a replay.  draws_in [RIAB_REPLAY_DRAWS][B] or NULL => Philox keyed by (seed; step, agent
+ * id) under tags of its own, the start position by the bounded rejection sampler of riab_agent_step; draws_out or NULL
+ * records the outcomes used (NaN where a draw was not taken).  Sham noise: z_in device float64 [K][2][B] or NULL => the
+ * sham agent's Philox stream (sham_seed; sham_step0 + k, agent id) exactly as riab_agent_step draws; z_out [K][2][B] or
+ * NULL; the caller advances sham_step0 by K per call.  steps_taken: device int32 [B], the sham steps the lane took in this
+ * call.  motion_diag: the sham agent's riab_agent_step counters (steps taken while waiting for the wave included).
+ * RIAB_EINVAL: null pointers, K < 1, dt-less or drifting motion, n_agents outside 0..B; RIAB_EALIGN: B % 4. */
+int riab_replay_agent_step(const RiabEnv* env, const RiabMotion* motion, const double* lead_state, double* sham_state,
+                           int64_t B, int64_t n_agents, int64_t agent_id0, int32_t* flag, double* replay_state, double t,
+                           double freq_dt, double mean_speed, double mean_duration, double speed_mean,
+                           const double* draws_in, double* draws_out, uint64_t seed, uint64_t step, const double* z_in,
+                           double* z_out, uint64_t sham_seed, uint64_t sham_step0, int32_t K, double* pos_out,
+                           int32_t* steps_taken, int32_t* motion_diag, int32_t* diag, riab_stream_t stream);
+
 /* ---- Rate maps and occupancy from the device history ----------------------------------------------------------------
  * The numbers behind Neurons.plot_rate_map(method="history") (Neurons.py:377-398, 479-490) and
  * Agent.plot_position_heatmap (Agent.py:951-956), i.e. utils.bin_data_for_histogramming (utils.py:544-589) =

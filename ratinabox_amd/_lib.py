@@ -124,6 +124,10 @@ POP_KINDS = {"place": 0, "grid": 1, "hdc": 2, "bvc": 3, "ovc": 4, "ff": 5, "velo
              "theta_place": 9, "plane_wave": 11}   # (10 is not assigned: riab_hip.h)
 THETA_NONE, THETA_BEHIND, THETA_AHEAD = 0, 1, 2                          # riab_hip.h RIAB_THETA_*
 THETA_DIAG_BEHIND, THETA_DIAG_AHEAD, THETA_DIAG_ROLLOUT, THETA_DIAG_FAR = range(4)
+DUMB_DIAG_WALL_CUTS, DUMB_DIAG_BOUNDARY, DUMB_DIAG_SATURATIONS = range(3)   # riab_hip.h RIAB_DUMB_DIAG_*
+RP_SPEED, RP_T_START, RP_T_END, RP_D_START, RP_LO, RP_HI, REPLAY_ROWS = 0, 1, 2, 3, 4, 7, 10   # riab_hip.h RIAB_RP_*
+RD_U, RD_SPEED, RD_DURATION, RD_POS_X, RD_POS_Y, RD_DIRECTION, REPLAY_DRAWS = range(7)         # riab_hip.h RIAB_RD_*
+REPLAY_DIAG_STARTED, REPLAY_DIAG_ENDED, REPLAY_DIAG_SATURATIONS, REPLAY_DIAG_RESAMPLE = range(4)
 EINVAL = -1
 EALIGN = -2
 ETOOBIG = -3
@@ -228,6 +232,14 @@ PROTOTYPES = {
                                               C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32,
                                               C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "riab_shift_agent_position": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
+    "riab_dumb_agent_step": (C.c_int, [C.POINTER(RiabEnv), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "riab_replay_agent_step": (C.c_int, [C.POINTER(RiabEnv), C.POINTER(RiabMotion), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         C.c_double, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                         C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "riab_history_bin_index": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "riab_history_rate_map_workspace": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64, C.c_int32]),

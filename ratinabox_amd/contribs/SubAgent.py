@@ -1,11 +1,12 @@
-"""`SubAgent`, `ThetaSequenceAgent`, `ShiftAgent`, `UnrelatedAgent` — Agents slaved to another Agent, on the device
-(reference ratinabox/contribs/SubAgent.py).
+"""`SubAgent`, `ThetaSequenceAgent`, `DumbAgent`, `ReplayAgent`, `ShiftAgent`, `UnrelatedAgent` — Agents slaved to another
+Agent, on the device (reference ratinabox/contribs/SubAgent.py).
 
 A SubAgent is an `Agent` of its lead's Environment whose position is a function of the lead's state: lane b of the
 SubAgent follows lane b of the lead (`n_agents`, `device` and `dt` are the lead's).  Its position is computed by a
-kernel of csrc/riab_theta_seq.hip from the lead's float64 state matrix and handed — a device tensor, nothing visits the
-host — to the forced-position step every Agent has (`riab_agent_step(forced_pos=...)`), so history, measured velocity
-and any `Neurons` population built on the SubAgent work as on any other Agent through their eager `update()`.
+kernel of csrc/riab_theta_seq.hip or csrc/riab_subagent.hip from the lead's float64 state matrix and handed — a device
+tensor, nothing visits the host — to the forced-position step every Agent has (`riab_agent_step(forced_pos=...)`), so
+history, measured velocity and any `Neurons` population built on the SubAgent work as on any other Agent through their
+eager `update()`.
 
 `ThetaSequenceAgent`: once per theta cycle (`theta_freq`) the position sweeps at `v_sequence` from `d_half` behind the
 lead, along the lead's own past, to `d_half` ahead of it, along a future simulated by the motion model from the lead's
@@ -23,15 +24,24 @@ of (distance, x, y) per lane: 24 bytes x lookback x agents (dt 2 ms, defaults: 3
 1 ms: 7812 records, 768 MB).  The future table is `[K + 1][3]` float64 per lane, K = ceil(4 forward_distance / (dt
 v_sequence)) + 8 steps: the bound on the reference's unbounded rollout loop (`theta_diagnostics["rollout_saturations"]`).
 
-Not built: `DumbAgent`, `ReplayAgent`, 1D environments, plotting.  A SubAgent cannot run inside `Agent.simulate()`, a
+`DumbAgent`: a wrong position on a spring round the lead (`drift_distance`, `drift_timescale`), cut short where a wall
+stands between the two, one launch per step.
+
+`ReplayAgent`: the lead's position, except while a lane "replays": it jumps to a random place, explores there at its
+replay speed and snaps back; `history["replay"]` flags those steps.  One launch per step; the replayed path is produced
+as it is consumed (two records per lane), not as the reference's up-front table.
+
+Not built: 1D environments, plotting.  A SubAgent cannot run inside `Agent.simulate()`, a
 step plan or a `TaskEnvironment`, nor follow a shard of a multi-GPU run (NotImplementedError)."""
 import copy
 import math
 import warnings
 
+import numpy as np
 import torch
 
 from .. import _lib as _L
+from .._history import HistoryView
 from ..Agent import Agent
 
 
@@ -226,6 +236,240 @@ class ThetaSequenceAgent(SubAgent):
         _L.check(rc, "riab_theta_sequence_step")
         self._n_records += 1
         self.last_theta_phase = phase
+        self._forced_step(self._pos_out)
+
+
+class DumbAgent(SubAgent):
+    """A wrong position that wanders round the lead as if attached to it by a spring (SubAgent.py:118-179).  In the
+    lead's frame the velocity of the displacement is an Ornstein-Uhlenbeck process of scale `sigma` and coherence time
+    `tau_v`, and a spring of stiffness `acceleration_scale` pulls the displacement back:
+
+        d = drift_distance    the typical distance between the two agents
+        tau_s = drift_timescale    how long the wrong position takes to journey round the true one
+        sigma = pi^2 d / tau_s^2,  tau_v = tau_s / 2,  acceleration_scale = sigma / d
+
+    A displacement that would cross a wall is cut to 95 % of the way to it, and the position obeys the Environment's
+    boundary conditions.  One kernel launch per step (csrc/riab_subagent.hip: riab_dumb_agent_step).
+
+    `update(noise=...)`: explicit standard normals `(2, B)` for this step (parity runs); otherwise the agent's own
+    Philox stream, a pure function of (its seed, its step index, the global agent id)."""
+
+    default_params = {
+        "drift_distance": 0.05,   # ~average distance between the two agents
+        "drift_timescale": 3.0,   # ~timescale over which the wrong position journeys around the true position
+    }
+
+    def __init__(self, LeadAgent, params={}):
+        self.params = copy.deepcopy(__class__.default_params)
+        self.params.update(params)
+        super().__init__(LeadAgent, self.params)
+        self.tau_v = self.drift_timescale / 2
+        self.sigma = math.pi ** 2 * self.drift_distance / (self.drift_timescale ** 2)
+        self.acceleration_scale = self.sigma / self.drift_distance
+        Bp, dev = self._Bp, self._device
+        self._disp = torch.zeros((2, Bp), dtype=torch.float64, device=dev)
+        self._dvel = torch.zeros((2, Bp), dtype=torch.float64, device=dev)
+        self._dumb_z = torch.zeros((2, Bp), dtype=torch.float64, device=dev)
+        self._ddiag = torch.zeros(4, dtype=torch.int32, device=dev)
+
+    # ---- read-outs -----------------------------------------------------------------------------------------------
+    def _lanes(self, t):
+        return self._squeeze(t[:, :self._B].t().cpu().numpy())
+
+    @property
+    def displacement(self):
+        """position - lead position, accounting for the environment: `(B, 2)`, or `(2,)` for one agent"""
+        return self._lanes(self._disp)
+
+    @property
+    def displacement_velocity(self):
+        return self._lanes(self._dvel)
+
+    @property
+    def displacement_tensors(self):
+        """(displacement, displacement velocity) on the device: float64 `[2, B_padded]` each"""
+        return self._disp, self._dvel
+
+    @property
+    def step_normals(self):
+        """The standard normals the last update() used: device float64 `[2, B_padded]`."""
+        return self._dumb_z
+
+    @property
+    def dumb_diagnostics(self):
+        """Counters of the step kernel over the real lanes: springs cut by a wall, positions the boundary conditions
+        changed, and of those the rejection sampler's saturations (polygonal rooms and holes)."""
+        d = self._ddiag.cpu().numpy()
+        return dict(wall_cuts=int(d[_L.DUMB_DIAG_WALL_CUTS]), boundary_corrections=int(d[_L.DUMB_DIAG_BOUNDARY]),
+                    resample_saturations=int(d[_L.DUMB_DIAG_SATURATIONS]))
+
+    # ---- one step ------------------------------------------------------------------------------------------------
+    def update(self, noise=None):
+        lead = self.LeadAgent
+        lead_state = self._lead_state()
+        dt = float(lead.dt)
+        # utils.ornstein_uhlenbeck(dt, x, drift=0, noise_scale=sigma, coherence_time=tau_v) (utils.py:361-368)
+        ou_sigma = math.sqrt((2 * self.sigma ** 2) / (self.tau_v * dt))
+        ou_theta = 1 / self.tau_v
+        z = self._as_device_f64(noise, 2) if noise is not None else None
+        env, _walls = self.Environment.device_tables(self._device)
+        rc = _L.lib.riab_dumb_agent_step(env, _L.ptr(lead_state), self._Bp, self._B, int(self.agent_id0), _L.ptr(self._disp),
+                                         _L.ptr(self._dvel), dt, ou_theta, ou_sigma, float(self.acceleration_scale), _L.ptr(z),
+                                         _L.ptr(self._dumb_z), int(self.rng_seed), int(self._step_index), _L.ptr(self._pos_out),
+                                         _L.ptr(self._ddiag), _L.current_stream())
+        _L.check(rc, "riab_dumb_agent_step")
+        self._keep_dumb = (z, _walls)
+        self.t = lead.t
+        self._forced_step(self._pos_out)
+
+
+class ReplayAgent(SubAgent):
+    """The lead's position, except during "replays": at rate `replay_freq` a lane detaches from its lead, jumps to a
+    random place, explores there with the motion model at a speed drawn round `replay_speed` for a time drawn round
+    `replay_duration`, and snaps back (SubAgent.py:358-432).
+
+    `self.ReplayAgent` is a sham Agent whose only use is the motion model of the replays; its motion parameters are the
+    ones passed to THIS agent.  The reference simulates a replay's whole path when it starts and interpolates that table
+    afterwards; here the path is produced as it is consumed: a lane keeps the two records that bracket its position and
+    its sham agent advances only as far as each update needs (csrc/riab_subagent.hip: riab_replay_agent_step, one launch
+    per update) — the same positions, since the distance along a replay only grows.  A lane's sham agent takes at most
+    `replay_steps_max` steps per update (default: 4 x the expected `replay_speed / speed_mean`, + 8); a lane that runs
+    out takes its newest record as its position and is counted in `replay_diagnostics["saturations"]`.
+
+    `update(draws=..., noise=...)` (parity runs): `draws` a dict of per-lane outcomes `u` (the trigger uniform), `speed`,
+    `duration`, `pos` (2, B), `direction` — read by the lanes that are outside a replay, the last four by those that
+    start one —; `noise` the standard normals `(K, 2, B)`, K = replay_steps_max, of the sham agent's steps of this
+    call.  Otherwise this agent's own Philox stream and the sham agent's."""
+
+    default_params = {
+        "replay_freq": 0.3,       # frequency of replay events, Hz
+        "replay_duration": 0.1,   # mean duration of replay events, s
+        "replay_speed": 1.0,      # mean speed of replay events, m/s
+    }
+
+    def __init__(self, LeadAgent, params={}, replay_steps_max=None):
+        self.params = copy.deepcopy(__class__.default_params)
+        self.params.update(params)
+        # the sham Agent (SubAgent.py:375-378): THIS agent's parameters without the three replay keys
+        sham_params = copy.deepcopy(self.params)
+        for key in __class__.default_params.keys():
+            sham_params.pop(key)
+        super().__init__(LeadAgent, self.params)
+        lead = self.LeadAgent
+        self.mean_replay_speed = self.replay_speed
+        self.mean_replay_duration = self.replay_duration
+        sham_params.update(dt=lead.dt, n_agents=lead.n_agents, device=lead.device)
+        self.ReplayAgent = Agent(self.Environment, sham_params)
+        self.ReplayAgent._auto_enabled = False
+        expected = self.mean_replay_speed / self.ReplayAgent.speed_mean   # sham steps per update: the dt cancels
+        self.replay_steps_max = int(replay_steps_max) if replay_steps_max is not None else int(math.ceil(4 * expected)) + 8
+        assert self.replay_steps_max >= 1
+        Bp, dev, K = self._Bp, self._device, self.replay_steps_max
+        self._flag = torch.zeros(Bp, dtype=torch.int32, device=dev)
+        self._rstate = torch.zeros((_L.REPLAY_ROWS, Bp), dtype=torch.float64, device=dev)
+        self._draws = torch.full((_L.REPLAY_DRAWS, Bp), float("nan"), dtype=torch.float64, device=dev)
+        self._replay_z = torch.zeros((K, 2, Bp), dtype=torch.float64, device=dev)
+        self._steps = torch.zeros(Bp, dtype=torch.int32, device=dev)
+        self._rdiag = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._flag_rows = torch.zeros((256, Bp), dtype=torch.bool, device=dev)
+        self._n_flag_rows = 0
+        self.history = HistoryView(tuple(self.history.keys()) + ("replay",), self._materialise_history,
+                                   lambda: (self._sync_plan(), self._hist.version)[1])
+
+    # ---- read-outs -----------------------------------------------------------------------------------------------
+    @property
+    def is_undergoing_replay(self):
+        """per lane: `(B,)` bool, or a bool for one agent (the device flags: `replay_flags`)"""
+        return self._squeeze(self._flag[:self._B].cpu().numpy().astype(bool))
+
+    @property
+    def replay_flags(self):
+        """device int32 `[B_padded]`: 1 in a replay"""
+        return self._flag
+
+    @property
+    def replay_state(self):
+        """device float64 `[10, B_padded]`: speed, start time, end time, the sham agent's distance at the start, and the
+        two records (distance since the start, x, y) a lane interpolates between (riab_hip.h RIAB_RP_*)"""
+        return self._rstate
+
+    @property
+    def replay_draws(self):
+        """What the last update() drew: device float64 `[6, B_padded]` rows u, speed, duration, x, y, direction; NaN where
+        a draw was not taken (u: lanes in a replay; the others: lanes that started none)."""
+        return self._draws
+
+    @property
+    def replay_normals(self):
+        """The standard normals of the sham agent's steps of the last update(): device float64 `[K, 2, B_padded]` (rows a
+        lane's wave did not reach keep older values)."""
+        return self._replay_z
+
+    @property
+    def replay_steps_taken(self):
+        """sham steps per lane in the last update(): device int32 `[B_padded]`"""
+        return self._steps
+
+    @property
+    def replay_diagnostics(self):
+        """Counters over the real lanes: replays started and ended, lane-steps that ran out of `replay_steps_max` sham
+        steps, start positions whose rejection sampler ran out of attempts."""
+        d = self._rdiag.cpu().numpy()
+        return dict(started=int(d[_L.REPLAY_DIAG_STARTED]), ended=int(d[_L.REPLAY_DIAG_ENDED]),
+                    saturations=int(d[_L.REPLAY_DIAG_SATURATIONS]), resample_saturations=int(d[_L.REPLAY_DIAG_RESAMPLE]))
+
+    def _materialise_history(self):
+        out = super()._materialise_history()
+        rows = self._flag_rows[:self._n_flag_rows, :self._B].cpu().numpy()
+        out["replay"] = rows[:, 0] if self._B == 1 else rows
+        return out
+
+    def reset_history(self):
+        super().reset_history()
+        self._n_flag_rows = 0
+
+    def _draws_tensor(self, draws):
+        """dict of per-lane outcomes -> device float64 `[6, Bp]` (padding lanes shadow lane 0)"""
+        B = self._B
+        rows = np.full((_L.REPLAY_DRAWS, self._Bp), np.nan)
+
+        def lane(x):
+            return (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x, dtype=np.float64)).astype(np.float64)
+
+        for key, row in (("u", _L.RD_U), ("speed", _L.RD_SPEED), ("duration", _L.RD_DURATION), ("direction", _L.RD_DIRECTION)):
+            rows[row, :B] = np.broadcast_to(lane(draws[key]).reshape(-1), (B,))
+        pos = lane(draws["pos"])
+        pos = pos.T if pos.shape == (B, 2) and B != 2 else pos.reshape(2, -1)
+        rows[_L.RD_POS_X:_L.RD_POS_Y + 1, :B] = np.broadcast_to(pos, (2, B))
+        rows[:, B:] = rows[:, :1]
+        return torch.from_numpy(rows).to(self._device)
+
+    # ---- one step ------------------------------------------------------------------------------------------------
+    def update(self, draws=None, noise=None):
+        lead, sham, K = self.LeadAgent, self.ReplayAgent, self.replay_steps_max
+        lead_state = self._lead_state()
+        t_now = float(self.t)   # the clock the reference compares with replay_end_time: this agent's own, as it was left
+        d_in = self._draws_tensor(draws) if draws is not None else None
+        z = sham._noise_tensor(noise, K) if noise is not None else None
+        m = sham._motion(float(lead.dt), False, 1, {})
+        env, _walls = self.Environment.device_tables(self._device)
+        rc = _L.lib.riab_replay_agent_step(env, m, _L.ptr(lead_state), _L.ptr(sham._state), self._Bp, self._B, int(sham.agent_id0),
+                                           _L.ptr(self._flag), _L.ptr(self._rstate), t_now, float(self.replay_freq * lead.dt),
+                                           float(self.mean_replay_speed), float(self.mean_replay_duration),
+                                           float(sham.speed_mean), _L.ptr(d_in), _L.ptr(self._draws), int(self.rng_seed),
+                                           int(self._step_index), _L.ptr(z), _L.ptr(self._replay_z), int(sham.rng_seed),
+                                           int(sham._step_index), K, _L.ptr(self._pos_out), _L.ptr(self._steps),
+                                           _L.ptr(sham._diag), _L.ptr(self._rdiag), _L.current_stream())
+        _L.check(rc, "riab_replay_agent_step")
+        sham._step_index += K       # whatever the lanes used: a lane's noise does not depend on the other lanes
+        sham._last_row = None       # (its state was written on the device)
+        self._keep_replay = (d_in, z, m, _walls)
+        if self.save_history:
+            if self._n_flag_rows == self._flag_rows.shape[0]:
+                self._flag_rows = torch.cat((self._flag_rows, torch.zeros_like(self._flag_rows)))
+            self._flag_rows[self._n_flag_rows] = self._flag != 0
+            self._n_flag_rows += 1
+        self.t = lead.t
         self._forced_step(self._pos_out)
 
 

@@ -5,7 +5,7 @@ the reference's way —
     from ratinabox_amd.contribs.ValueNeuron import ValueNeuron
     from ratinabox_amd.contribs.SuccessorFeatures import SuccessorFeatures
     from ratinabox_amd.contribs.PhasePrecessingPlaceCells import PhasePrecessingPlaceCells
-    from ratinabox_amd.contribs.SubAgent import SubAgent, ThetaSequenceAgent, ShiftAgent, UnrelatedAgent
+    from ratinabox_amd.contribs.SubAgent import SubAgent, ThetaSequenceAgent, DumbAgent, ReplayAgent, ShiftAgent, UnrelatedAgent
     from ratinabox_amd.contribs.PlaneWaveNeurons import PlaneWaveNeurons
 """
 __all__ = ["TaskEnvironment", "ValueNeuron", "SuccessorFeatures", "PhasePrecessingPlaceCells", "SubAgent", "PlaneWaveNeurons"]
