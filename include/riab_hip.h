@@ -421,6 +421,34 @@ int riab_feedforward(const RiabFFInput* inputs, int32_t n_inputs, const float* b
                      int64_t T, int64_t B, int32_t activation, const float* act_params, float* out,
                      float* out_prime, riab_stream_t stream);
 
+/* contribs.NeuralNetworkNeurons: a whole multi-layer perceptron in ONE launch (csrc/riab_mlp.hip).
+ *   h_0 = the input populations' rates, concatenated in order along the cell axis
+ *   h_i = act_i(W_i h_{i-1} + bias_i)        out = h_{n_layers}
+ * The first layer streams its operands from memory in K slabs like riab_feedforward; every later layer takes its B
+ * operand from the accumulator registers of the layer before it, so no hidden activation is ever written to memory.
+ * The weights are torch.nn.Linear's own tensors READ IN PLACE (row-major [n_out][n_in], no padding, no transposed copy):
+ * an optimiser step is seen by the next launch.  A position's result depends on its inputs and the weights only (not on
+ * T, B or where its tile lies): a row of a many-row launch has the bits of the same row launched alone. */
+#define RIAB_MLP_MAX_LAYERS 8
+#define RIAB_MLP_MAX_HIDDEN 128
+typedef struct RiabMLPLayer {
+  const float* w;       /* device float32 [n_out][n_in], row-major: torch.nn.Linear.weight, READ IN PLACE */
+  const float* bias;    /* device float32 [n_out], or NULL */
+  int32_t n_in, n_out;
+  int32_t activation;   /* RIAB_ACT_* */
+  float act_params[4];  /* as riab_feedforward */
+} RiabMLPLayer;
+
+/* inputs[l]: device float32 [T][input_n[l]][B] (16-byte aligned, B % 4 == 0), as RiabFFInput.rates; sum(input_n) ==
+ * layers[0].n_in; layers[i].n_in == layers[i-1].n_out; out: device float32 [T][layers[n_layers-1].n_out][B].
+ * At most 8 inputs and RIAB_MLP_MAX_LAYERS layers; every HIDDEN width (n_out of every layer but the last) at most
+ * RIAB_MLP_MAX_HIDDEN; the first layer's n_in and the last layer's n_out are not bounded; T <= 65535.
+ * Errors (nothing is launched): RIAB_EINVAL null pointer / non-positive size / broken width chain / unknown activation;
+ * RIAB_EALIGN B % 4 or a misaligned inputs[l] / out; RIAB_ETOOBIG a limit above. */
+int riab_mlp_forward(const float* const* inputs, const int32_t* input_n, int32_t n_inputs,
+                     const RiabMLPLayer* layers, int32_t n_layers,
+                     int64_t T, int64_t B, float* out, riab_stream_t stream);
+
 /* ---- step plans: the closed-loop per-step path as one native call -----------------------------
  * `for each step: Agent.update(); N.update() for N in Agent.Neurons` (demos/simple_example.ipynb
  * cell 4; contribs/TaskEnvironment.py:399-408) recorded once, then advanced by riab_plan_step:
@@ -1293,7 +1321,7 @@ int riab_history_rate_map_finish(const double* sums, const int64_t* counts, int3
                                  int32_t norm_by_bincount, double* maps, uint8_t* zero_bins, riab_stream_t stream);
 
 /* sizeof of the ABI's structs as compiled into the library (which: 0 RiabEnv, 1 RiabMotion, 2 RiabRateIO,
- * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at
+ * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer, 11 RiabMLPLayer; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at
  * load */
 int64_t riab_abi_sizeof(int32_t which);
 

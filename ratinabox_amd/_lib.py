@@ -55,6 +55,12 @@ class RiabFFInput(C.Structure):
     _fields_ = [("rates", C.c_void_p), ("wt", C.c_void_p), ("n_in", C.c_int32)]
 
 
+class RiabMLPLayer(C.Structure):
+    """One layer of riab_mlp_forward (contribs.NeuralNetworkNeurons): include/riab_hip.h RiabMLPLayer."""
+    _fields_ = [("w", C.c_void_p), ("bias", C.c_void_p), ("n_in", C.c_int32), ("n_out", C.c_int32),
+                ("activation", C.c_int32), ("act_params", C.c_float * 4)]
+
+
 class RiabTDParams(C.Structure):
     """The constants of a TD learner (contribs.ValueNeuron): include/riab_hip.h RiabTDParams."""
     _fields_ = [("dt", C.c_float), ("tau", C.c_float), ("tau_e", C.c_float), ("eta", C.c_float), ("L2", C.c_float),
@@ -145,6 +151,7 @@ CTRL_STARTED, CTRL_TIMEOUTS, CTRL_ABORT, CTRL_SERIALISED, CTRL_STAMPS, CTRL_TRAJ
 STEP1_SYNC_STRIDE, STEP1_SYNC_TAIL, STEP1_SYNC_TIMEOUTS = 64, 16, 0   # riab_hip.h RIAB_STEP1_SYNC_*
 STEP1_SYNC_FIRST_BAD, STEP1_SYNC_LAST_BAD, STEP1_SYNC_FATAL = 1, 2, 3
 STEP1_MAX_POPS = 4                                                      # csrc/riab_device.h RIAB_STEP1_MAX_POPS
+MLP_MAX_LAYERS, MLP_MAX_HIDDEN = 8, 128                                  # riab_hip.h RIAB_MLP_MAX_*
 WALL_GRID_MAX = 16                                                      # riab_hip.h RIAB_WALL_GRID_MAX
 RATEMAP_MAX_BINS, RATEMAP_DROPPED, RATEMAP_FP32_RUN = 4096, 0xFFFF, 0     # riab_hip.h RIAB_RATEMAP_*
 CU_PROBE_WORDS = 4097                                                   # riab_hip.h RIAB_CU_PROBE_WORDS
@@ -211,6 +218,8 @@ PROTOTYPES = {
                                     C.c_uint64, C.c_uint64, C.c_int32, C.c_int64, C.c_void_p]),
     "riab_feedforward": (C.c_int, [C.POINTER(RiabFFInput), C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                    C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "riab_mlp_forward": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.POINTER(RiabMLPLayer), C.c_int32,
+                                   C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "riab_td_forward_tail": (C.c_int, [C.POINTER(RiabTDParams), C.POINTER(RiabTDLayer), C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p]),
     "riab_td_workspace": (C.c_int64, [C.POINTER(RiabTDParams), C.POINTER(RiabTDLayer), C.c_int32]),
@@ -340,7 +349,7 @@ def _load():
     # the ctypes mirrors must have the layouts the library was compiled with (a stale library with the same
     # version number would otherwise corrupt memory silently)
     mirrors = ((0, RiabEnv), (1, RiabMotion), (2, RiabRateIO), (3, RiabPopulation), (4, RiabTask), (5, RiabFFInput),
-               (7, RiabSimulate), (8, RiabWatch), (9, RiabTDParams), (10, RiabTDLayer))
+               (7, RiabSimulate), (8, RiabWatch), (9, RiabTDParams), (10, RiabTDLayer), (11, RiabMLPLayer))
     for which, cls in mirrors:
         if lib.riab_abi_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"libriab_hip.so: sizeof({cls.__name__}) is {lib.riab_abi_sizeof(which)} in the library, "

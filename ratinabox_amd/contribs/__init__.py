@@ -7,5 +7,7 @@ the reference's way —
     from ratinabox_amd.contribs.PhasePrecessingPlaceCells import PhasePrecessingPlaceCells
     from ratinabox_amd.contribs.SubAgent import SubAgent, ThetaSequenceAgent, DumbAgent, ReplayAgent, ShiftAgent, UnrelatedAgent
     from ratinabox_amd.contribs.PlaneWaveNeurons import PlaneWaveNeurons
+    from ratinabox_amd.contribs.NeuralNetworkNeurons import NeuralNetworkNeurons, MultiLayerPerceptron
 """
-__all__ = ["TaskEnvironment", "ValueNeuron", "SuccessorFeatures", "PhasePrecessingPlaceCells", "SubAgent", "PlaneWaveNeurons"]
+__all__ = ["TaskEnvironment", "ValueNeuron", "SuccessorFeatures", "PhasePrecessingPlaceCells", "SubAgent", "PlaneWaveNeurons",
+           "NeuralNetworkNeurons"]

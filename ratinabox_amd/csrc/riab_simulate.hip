@@ -855,6 +855,7 @@ extern "C" int64_t riab_abi_sizeof(int32_t which) {
     case 8: return (int64_t)sizeof(RiabWatch);
     case 9: return (int64_t)sizeof(RiabTDParams);
     case 10: return (int64_t)sizeof(RiabTDLayer);
+    case 11: return (int64_t)sizeof(RiabMLPLayer);
     default: return -1;
   }
 }

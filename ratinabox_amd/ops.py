@@ -15,6 +15,7 @@ Functional operators (return a new tensor)
     place_cells, grid_cells, plane_wave_neurons, head_direction_cells, boundary_vector_cells   rates float32 (n, P)
     spikes                                                              uint8 (T, n, B) from rates (T, n, B)
     feedforward                                                         float32 (T, n_out, B)
+    mlp_forward   a whole multi-layer perceptron in one launch (contribs.NeuralNetworkNeurons)   float32 (T, n_out, B)
 In-place operators
     td_forward_tail  the tail of ValueNeuron.update(): dV/dt, V_last and (optionally) the eligibility traces
     td_update        ValueNeuron.update_weights(reward): TD error, batch-mean gradient on the matrix cores, W^T updated
@@ -239,6 +240,56 @@ def feedforward(inputs: List[Tensor], weights_t: List[Tensor], bias: Tensor, act
     out = torch.empty((T, n_out, B), dtype=torch.float32, device=inputs[0].device)
     _L.check(_L.lib.riab_feedforward(arr, len(inputs), _L.ptr(bias), n_out, T, B, int(activation), pars, _L.ptr(out), None,
                                      _L.current_stream()), "riab_feedforward")
+    return out
+
+
+# ---- contribs.NeuralNetworkNeurons: a whole multi-layer perceptron in one launch -----------------------------------
+def mlp_launch(inputs, weights, biases, activations, act_params, out, stream):
+    """riab_mlp_forward on device tensors, written into `out` float32 (T, n_out, B): inputs[l] contiguous float32
+    (T, n_l, B); weights[i] float32 (n_out_i, n_in_i) = nn.Linear.weight, READ IN PLACE (their data_ptr()s are taken here,
+    at every call); biases[i] float32 (n_out_i,) or None; activations[i] RIAB_ACT_*; act_params[i] 4 floats."""
+    n_in, n_l = len(inputs), len(weights)
+    if not n_in or not n_l or len(biases) != n_l or len(activations) != n_l or len(act_params) != n_l:
+        raise ValueError("one weight, one bias entry, one activation and 4 activation parameters per layer; >= 1 input")
+    T, _, B = (int(x) for x in inputs[0].shape)
+    ptrs, widths = (C.c_void_p * n_in)(), (C.c_int32 * n_in)()
+    for l, x in enumerate(inputs):
+        if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous() or x.shape[0] != T or x.shape[2] != B:
+            raise ValueError("inputs must be contiguous float32 (T, n_in, B) with equal T and B")
+        ptrs[l], widths[l] = x.data_ptr(), int(x.shape[1])
+    arr = (_L.RiabMLPLayer * n_l)()
+    for i, (w, b) in enumerate(zip(weights, biases)):
+        if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous() or w.device != inputs[0].device:
+            raise ValueError("weights[i] must be a contiguous float32 tensor (n_out, n_in) on the inputs' device")
+        if b is not None and (b.dtype != torch.float32 or tuple(b.shape) != (w.shape[0],) or not b.is_contiguous()
+                              or b.device != w.device):
+            raise ValueError("biases[i] must be None or a contiguous float32 tensor (n_out,) on the weights' device")
+        q = arr[i]
+        q.w, q.bias = w.data_ptr(), (b.data_ptr() if b is not None else None)
+        q.n_out, q.n_in, q.activation = int(w.shape[0]), int(w.shape[1]), int(activations[i])
+        for k in range(4):
+            q.act_params[k] = float(act_params[i][k])
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != T * int(weights[-1].shape[0]) * B:
+        raise ValueError("out must be a contiguous float32 tensor (T, n_out, B)")
+    _L.check(_L.lib.riab_mlp_forward(ptrs, widths, n_in, arr, n_l, T, B, _L.ptr(out), stream), "riab_mlp_forward")
+
+
+@_register("mlp_forward(Tensor[] inputs, Tensor[] weights, Tensor?[] biases, int[] activations, float[] act_params) -> Tensor",
+           lambda inputs, weights, biases, activations, act_params:
+           inputs[0].new_empty((inputs[0].shape[0], weights[-1].shape[0], inputs[0].shape[2])))
+def mlp_forward(inputs: List[Tensor], weights: List[Tensor], biases: List[Optional[Tensor]], activations: List[int],
+                act_params: List[float]) -> Tensor:
+    """A multi-layer perceptron in ONE launch (riab_mlp_forward, csrc/riab_mlp.hip): h_0 = the inputs concatenated along
+    the cell axis, h_i = act_i(weights_i @ h_{i-1} + biases_i), hidden activations kept in registers.  inputs_l float32
+    (T, n_l, B), B % 4 == 0; weights_i float32 (n_out_i, n_in_i) — nn.Linear.weight as it is, read in place —; biases_i
+    float32 (n_out_i,) or None; activations_i RIAB_ACT_*; act_params 4 floats per layer, flat.  At most 8 inputs and 8
+    layers, hidden widths <= 128.  Forward only (no autograd formula).  Returns float32 (T, n_out, B)."""
+    if len(act_params) != 4 * len(weights):
+        raise ValueError("act_params holds 4 floats per layer")
+    out = torch.empty((int(inputs[0].shape[0]), int(weights[-1].shape[0]), int(inputs[0].shape[2])), dtype=torch.float32,
+                      device=inputs[0].device)
+    mlp_launch(inputs, weights, biases, activations, [act_params[4 * i:4 * i + 4] for i in range(len(weights))], out,
+               _L.current_stream())
     return out
 
 
