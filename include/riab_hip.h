@@ -30,9 +30,10 @@
 extern "C" {
 #endif
 
-#define RIAB_ABI_VERSION 11    /* (the riab_history_* entry points were added at 11 without a bump: they are new exports
-                                * only; no struct, enum value or existing signature changed, so an older binding still
-                                * loads this library and a newer one finds a missing export at load time) */
+#define RIAB_ABI_VERSION 11    /* (the riab_history_* entry points, riab_history_moments among them, were added at 11
+                                * without a bump: they are new exports only; no struct, enum value or existing signature
+                                * changed, so an older binding still loads this library and a newer one finds a missing
+                                * export at load time) */
 #define RIAB_MAX_WALLS 64     /* walls staged in LDS by the motion / BVC / line-of-sight kernels */
 #define RIAB_MAX_TEST_ANGLES 360
 #define RIAB_STATE_ROWS 12    /* rows of the agent state matrix, see below */
@@ -1320,8 +1321,44 @@ int riab_history_rate_map(const void* rows, int32_t rows_are_spikes, int64_t T, 
 int riab_history_rate_map_finish(const double* sums, const int64_t* counts, int32_t n, int32_t n_bins,
                                  int32_t norm_by_bincount, double* maps, uint8_t* zero_bins, riab_stream_t stream);
 
+/* ---- Linear decoders fitted from the device history --------------------------------------------------------------------
+ * The reference's decoding workflow (tests/test_advanced.py::test_decoding_position, demos/decoding_position_example)
+ * copies history["firingrate"] and history["pos"] to the host and fits sklearn.linear_model.Ridge.  Here one call adds
+ * the moment matrix of the AUGMENTED sample vector
+ *   z(t, b) = [ rates of input 0 ; ... ; rates of input n_inputs-1 ; the target rows of the trajectory record ; 1 ]
+ * (m = sum of inputs[l].n + n_targets + 1 entries) over the samples of the rows given:
+ *   moments[i][j] += sum over (t in 0, t_step, 2 t_step, ... < T; b < n_real) of z_i z_j        device float64 [m][m]
+ * X^T X is its top-left block, X^T y the columns of the targets, the column sums its last row, the number of samples
+ * moments[m-1][m-1].  ACCUMULATED IN PLACE (zeroed by the caller before the first call): a history spread over several
+ * chunks is handed over piece by piece, and the moments of two shards or two time windows may simply be added.
+ * Products and sums are float64 on the matrix cores (v_mfma_f64_16x16x4_f64; the fp32 rates are widened exactly).
+ * A sample is left out entirely — its 1 included — when b >= n_real (a padding lane) or when any of its target values
+ * is not finite; the latter are counted in *n_dropped (device int64, ADDED to).  Nothing of a sample left out is
+ * multiplied or added: its lanes may hold NaN or anything else in any row.  The samples are split over workgroups by a
+ * rule of the shape alone, each split's float64 partial goes to `workspace` and the partials are added in split order:
+ * no floating-point atomic, the same call on the same data gives the same bits.  The result is the full symmetric
+ * matrix (only tile pairs i >= j are multiplied; the finishing kernel mirrors them). */
+#define RIAB_MOMENTS_MAX_TARGETS 4
+#define RIAB_MOMENTS_MAX_M 4096        /* rows of z a call takes (the workspace grows with m^2) */
+typedef struct RiabMomentInput {
+  const float* rows;   /* device float32 [T][n][B], 16-byte aligned: a population's rate history (RiabFFInput.rates) */
+  int32_t n;           /* >= 1 */
+} RiabMomentInput;
+
+/* Doubles of workspace riab_history_moments needs (positive, non-decreasing in T, m and B), or a negative RIAB_E* code. */
+int64_t riab_history_moments_workspace(int64_t T, int64_t t_step, int32_t m, int64_t B);
+
+/* traj: device float32 [T][RIAB_HIST_ROWS][B] of the same steps; target_rows: HOST, n_targets (1..RIAB_MOMENTS_MAX_TARGETS)
+ * indices RIAB_H_* into it.  T = 0 launches nothing.  Checked before anything is launched: RIAB_EINVAL null pointers,
+ * n_inputs outside 1..RIAB_FF_MAX_INPUTS, n_targets outside 1..RIAB_MOMENTS_MAX_TARGETS, a target row outside
+ * 0..RIAB_HIST_ROWS-1, inputs[l].n < 1, t_step < 1, n_real outside 0..B; RIAB_EALIGN B % 4 or a misaligned pointer;
+ * RIAB_ETOOBIG m > RIAB_MOMENTS_MAX_M or T * B / 4 >= 2^31 - 1 (split the rows). */
+int riab_history_moments(const RiabMomentInput* inputs, int32_t n_inputs, const float* traj, const int32_t* target_rows,
+                         int32_t n_targets, int64_t T, int64_t t_step, int64_t B, int64_t n_real, double* moments,
+                         int64_t* n_dropped, double* workspace, riab_stream_t stream);
+
 /* sizeof of the ABI's structs as compiled into the library (which: 0 RiabEnv, 1 RiabMotion, 2 RiabRateIO,
- * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer, 11 RiabMLPLayer; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at
+ * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer, 11 RiabMLPLayer, 12 RiabMomentInput; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at
  * load */
 int64_t riab_abi_sizeof(int32_t which);
 

@@ -527,6 +527,12 @@ class Neurons:
                                               position_data_agent)
         return maps.cpu().numpy(), zero.cpu().numpy()
 
+    def fit_decoder(self, **kw):
+        """A ridge decoder from this population's recorded rates to the agent's recorded target (`_decoder.
+        fit_linear_decoder([self], **kw)`: target="pos", t_start, t_end, stride, alpha=0.01), fitted on the device."""
+        from ._decoder import fit_linear_decoder
+        return fit_linear_decoder([self], **kw)
+
     def reset_history(self):
         if self.Agent._plan is not None:
             self.Agent._plan.close()  # (its open rows live in the chunks dropped here)

@@ -61,6 +61,11 @@ class RiabMLPLayer(C.Structure):
                 ("activation", C.c_int32), ("act_params", C.c_float * 4)]
 
 
+class RiabMomentInput(C.Structure):
+    """One population history of riab_history_moments: include/riab_hip.h RiabMomentInput."""
+    _fields_ = [("rows", C.c_void_p), ("n", C.c_int32)]
+
+
 class RiabTDParams(C.Structure):
     """The constants of a TD learner (contribs.ValueNeuron): include/riab_hip.h RiabTDParams."""
     _fields_ = [("dt", C.c_float), ("tau", C.c_float), ("tau_e", C.c_float), ("eta", C.c_float), ("L2", C.c_float),
@@ -154,6 +159,7 @@ STEP1_MAX_POPS = 4                                                      # csrc/r
 MLP_MAX_LAYERS, MLP_MAX_HIDDEN = 8, 128                                  # riab_hip.h RIAB_MLP_MAX_*
 WALL_GRID_MAX = 16                                                      # riab_hip.h RIAB_WALL_GRID_MAX
 RATEMAP_MAX_BINS, RATEMAP_DROPPED, RATEMAP_FP32_RUN = 4096, 0xFFFF, 0     # riab_hip.h RIAB_RATEMAP_*
+MOMENTS_MAX_TARGETS, MOMENTS_MAX_M = 4, 4096                            # riab_hip.h RIAB_MOMENTS_MAX_*
 CU_PROBE_WORDS = 4097                                                   # riab_hip.h RIAB_CU_PROBE_WORDS
 STEP1_MAIL_STRIDE = 1088                                                # riab_hip.h RIAB_STEP1_MAIL_STRIDE
 
@@ -256,6 +262,10 @@ PROTOTYPES = {
                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "riab_history_rate_map_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
+    "riab_history_moments_workspace": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int64]),
+    "riab_history_moments": (C.c_int, [C.POINTER(RiabMomentInput), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
+                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "riab_fill": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "riab_plan_create": (C.c_void_p, [C.POINTER(RiabEnv), C.POINTER(RiabMotion), C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
@@ -349,7 +359,7 @@ def _load():
     # the ctypes mirrors must have the layouts the library was compiled with (a stale library with the same
     # version number would otherwise corrupt memory silently)
     mirrors = ((0, RiabEnv), (1, RiabMotion), (2, RiabRateIO), (3, RiabPopulation), (4, RiabTask), (5, RiabFFInput),
-               (7, RiabSimulate), (8, RiabWatch), (9, RiabTDParams), (10, RiabTDLayer), (11, RiabMLPLayer))
+               (7, RiabSimulate), (8, RiabWatch), (9, RiabTDParams), (10, RiabTDLayer), (11, RiabMLPLayer), (12, RiabMomentInput))
     for which, cls in mirrors:
         if lib.riab_abi_sizeof(which) != C.sizeof(cls):
             raise ImportError(f"libriab_hip.so: sizeof({cls.__name__}) is {lib.riab_abi_sizeof(which)} in the library, "

@@ -15,28 +15,41 @@ from . import utils
 MAX_QUADS = (1 << 31) - 2   # riab_history_*: T * B / 4 of one call stays below 2^31 - 1
 
 
+def history_pieces(filled, start, stop, stride=1, max_rows=None):
+    """The rows range(start, stop, stride) of several histories of the same steps whose chunk boundaries need not
+    coincide, as pieces that lie in ONE chunk of each: a list of (first rows, length) where `first rows` is one (chunk,
+    row in it) per history and the piece's rows 0, stride, 2 stride, ... < length are the selected ones — the stride
+    keeps its phase across chunk and piece boundaries.  `filled`: the rows used per chunk, one list per history
+    (DeviceHistory.filled); `max_rows`: the longest piece one call takes."""
+    start, stop, stride = int(start), int(stop), int(stride)
+    if stride < 1:
+        raise ValueError(f"stride must be >= 1, got {stride}")
+    if start < 0 or stop > min(sum(f) for f in filled):
+        raise ValueError(f"rows [{start}, {stop}) are not in every history ({[sum(f) for f in filled]} rows)")
+    limit = None if max_rows is None else max(1, int(max_rows))
+    out = []
+    idx = [0] * len(filled)    # current chunks
+    base = [0] * len(filled)   # global row of their first rows
+    g = start
+    while g < stop:
+        for h, f in enumerate(filled):
+            while g >= base[h] + f[idx[h]]:
+                base[h] += f[idx[h]]
+                idx[h] += 1
+        end = min([stop] + [base[h] + f[idx[h]] for h, f in enumerate(filled)])
+        if limit is not None:
+            end = min(end, g + limit)
+        length = (end - 1 - g) // stride * stride + 1     # up to the last selected row of [g, end)
+        out.append(([(idx[h], g - base[h]) for h in range(len(filled))], length))
+        g += (length - 1) + stride                        # the next selected row
+    return out
+
+
 def history_segments(filled_a, filled_p, start, stop):
     """The rows [start, stop) of two histories of the same steps whose chunk boundaries need not coincide, as pieces
     that lie in ONE chunk of each: a list of (agent chunk, first row in it, population chunk, first row in it, length).
     `filled_a` / `filled_p`: the rows used per chunk (DeviceHistory.filled)."""
-    start, stop = int(start), int(stop)
-    if start < 0 or stop > min(sum(filled_a), sum(filled_p)):
-        raise ValueError(f"rows [{start}, {stop}) are not in both histories ({sum(filled_a)} and {sum(filled_p)} rows)")
-    out = []
-    ia = ip = 0          # current chunks
-    a0 = p0 = 0          # global row of their first rows
-    g = start
-    while g < stop:
-        while g >= a0 + filled_a[ia]:
-            a0 += filled_a[ia]
-            ia += 1
-        while g >= p0 + filled_p[ip]:
-            p0 += filled_p[ip]
-            ip += 1
-        n = min(stop, a0 + filled_a[ia], p0 + filled_p[ip]) - g
-        out.append((ia, g - a0, ip, g - p0, n))
-        g += n
-    return out
+    return [(ca, ra, cp, rp, n) for ((ca, ra), (cp, rp)), n in history_pieces([filled_a, filled_p], start, stop)]
 
 
 def _edge_tensors(extent, dx):

@@ -856,6 +856,7 @@ extern "C" int64_t riab_abi_sizeof(int32_t which) {
     case 9: return (int64_t)sizeof(RiabTDParams);
     case 10: return (int64_t)sizeof(RiabTDLayer);
     case 11: return (int64_t)sizeof(RiabMLPLayer);
+    case 12: return (int64_t)sizeof(RiabMomentInput);
     default: return -1;
   }
 }

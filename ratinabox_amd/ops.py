@@ -17,6 +17,7 @@ Functional operators (return a new tensor)
     feedforward                                                         float32 (T, n_out, B)
     mlp_forward   a whole multi-layer perceptron in one launch (contribs.NeuralNetworkNeurons)   float32 (T, n_out, B)
 In-place operators
+    history_moments  the float64 moment matrix of [rates ; targets ; 1] over history rows: what a ridge decoder is solved from
     td_forward_tail  the tail of ValueNeuron.update(): dV/dt, V_last and (optionally) the eligibility traces
     td_update        ValueNeuron.update_weights(reward): TD error, batch-mean gradient on the matrix cores, W^T updated
     td_learn_step    ValueNeuron.learn(reward) behind the forward pass + reset(lanes=mask), in two launches
@@ -606,3 +607,41 @@ def history_rate_map_finish(sums: Tensor, counts: Tensor, norm_by_bincount: bool
                                                  _L.ptr(maps), _L.ptr(zero), _L.current_stream()),
              "riab_history_rate_map_finish")
     return maps, zero
+
+
+# ---- linear decoders from the history: riab_history_moments ----------------------------------------------------------
+@_register("history_moments(Tensor[] inputs, Tensor traj, int[] target_rows, int t_step, int n_real, Tensor(a!) moments, "
+           "Tensor(b!) n_dropped) -> ()", lambda inputs, traj, target_rows, t_step, n_real, moments, n_dropped: None)
+def history_moments(inputs: List[Tensor], traj: Tensor, target_rows: List[int], t_step: int, n_real: int, moments: Tensor,
+                    n_dropped: Tensor) -> None:
+    """The moment matrix a ridge decoder is solved from (riab_history_moments, float64 matrix cores), in place:
+    moments += sum of z z^T over the samples (t in 0, t_step, 2 t_step, ...; b < n_real) of z = [inputs_0[t, :, b] ; ... ;
+    traj[t, target_rows, b] ; 1].  inputs_l: float32 (T, n_l, B) rate rows; traj: float32 (T, 8, B) of the same steps;
+    moments: float64 (m, m), m = sum n_l + len(target_rows) + 1, ADDED to; n_dropped: int64 (1,), ADDED to: the samples
+    left out because a target value was not finite (padding lanes b >= n_real are left out and not counted)."""
+    if not inputs or len(inputs) > 8:
+        raise ValueError("1..8 input histories")
+    if traj.dtype != torch.float32 or traj.dim() != 3 or traj.shape[1] != _L.HIST_ROWS or not traj.is_contiguous():
+        raise ValueError("traj must be a contiguous float32 tensor (T, 8, B)")
+    T, B = int(traj.shape[0]), int(traj.shape[2])
+    arr = (_L.RiabMomentInput * len(inputs))()
+    m = len(target_rows) + 1
+    for l, x in enumerate(inputs):
+        if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous() or x.shape[0] != T or x.shape[2] != B or \
+                x.device != traj.device:
+            raise ValueError("inputs must be contiguous float32 (T, n_l, B) tensors of traj's steps, lanes and device")
+        arr[l].rows, arr[l].n = x.data_ptr(), int(x.shape[1])
+        m += int(x.shape[1])
+    if moments.dtype != torch.float64 or tuple(moments.shape) != (m, m) or not moments.is_contiguous() or \
+            moments.device != traj.device:
+        raise ValueError(f"moments must be a contiguous float64 tensor ({m}, {m}) on traj's device")
+    if n_dropped.dtype != torch.int64 or n_dropped.numel() != 1 or n_dropped.device != traj.device:
+        raise ValueError("n_dropped must be an int64 tensor of one element on traj's device")
+    need = int(_L.lib.riab_history_moments_workspace(T, int(t_step), m, B))
+    if need < 0:
+        raise _L.RiabError(f"riab_history_moments_workspace failed with code {need}: {_L.strerror(need)}")
+    ws = torch.empty(max(need, 1), dtype=torch.float64, device=traj.device)
+    rows = (C.c_int32 * len(target_rows))(*[int(r) for r in target_rows])
+    _L.check(_L.lib.riab_history_moments(arr, len(inputs), _L.ptr(traj), rows, len(target_rows), T, int(t_step), B,
+                                         int(n_real), _L.ptr(moments), _L.ptr(n_dropped), _L.ptr(ws), _L.current_stream()),
+             "riab_history_moments")
