@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RIAB_ABI_VERSION 11    /* (the riab_history_* entry points, riab_history_moments among them, were added at 11
+#define RIAB_ABI_VERSION 11    /* (the riab_history_* entry points, riab_history_moments among them, and riab_gp_predict were added at 11
                                 * without a bump: they are new exports only; no struct, enum value or existing signature
                                 * changed, so an older binding still loads this library and a newer one finds a missing
                                 * export at load time) */
@@ -1356,6 +1356,35 @@ int64_t riab_history_moments_workspace(int64_t T, int64_t t_step, int32_t m, int
 int riab_history_moments(const RiabMomentInput* inputs, int32_t n_inputs, const float* traj, const int32_t* target_rows,
                          int32_t n_targets, int64_t T, int64_t t_step, int64_t B, int64_t n_real, double* moments,
                          int64_t* n_dropped, double* workspace, riab_stream_t stream);
+
+/* ---- Gaussian-process decoders run on the device history -----------------------------------------------------------------
+ * The reference decodes with sklearn.gaussian_process.GaussianProcessRegressor(alpha, RBF(l)) beside its Ridge.  The fit
+ * (a Cholesky solve of the N x N kernel matrix) is done by the caller; this is the predictive mean over history rows:
+ *   out[t][d][b] = sum over j < n_train of exp(-max(0, |x*|^2 + |x_j|^2 - 2 x*.x_j) * inv_two_ell2) * alpha[d][j]
+ * where x* is the concatenation over the inputs of rates_l[t][:][b].  (A new export at ABI 11, like the riab_history_*
+ * entry points: no struct, enum value or existing signature changes.)
+ *   inputs[l].rates  device float32 [T][n_in][B]: a population's rows, as riab_feedforward takes them
+ *   inputs[l].wt     device float32 [n_in][Np]: the training matrix of that population TRANSPOSED (wt[k][j] = cell k of
+ *                    training sample j), Np = n_train rounded up to a multiple of 32, columns j >= n_train zero
+ *   sq_train         device float32 [Np]: |x_j|^2 over all the inputs, zero padded
+ *   alpha            device float32 [n_out][Np]: the dual coefficients, zero padded; n_out = 1..RIAB_GP_MAX_OUT
+ *   inv_two_ell2     1 / (2 l^2), finite and > 0
+ *   out              device float32 [T][n_out][B]
+ * The cross term runs on v_mfma_f32_32x32x2_f32 (exact fp32 accumulation, k ascending); |x*|^2 is summed from the slabs
+ * as they stream through LDS; the exponential (v_exp_f32) and the contraction with alpha are fused behind each block of
+ * training samples, so no T B x N intermediate reaches memory.  The clamp at 0 is part of the contract (the GEMM form can
+ * come out slightly negative; the kernel value never exceeds 1).  Positions are columns: whatever a padding lane holds
+ * stays in its own column, and a lane whose |x*|^2 is not finite (a NaN, an infinite or an overflowing rate) is written as
+ * NaN, that sample alone.  Fixed summation order, no atomics, N is not split over workgroups (no workspace); the
+ * instruction sequence of a position depends on neither T, B nor its place: a row decoded alone has the bits of the same
+ * row inside a many-row call.  T = 0 launches nothing.
+ * Checked before anything is launched: RIAB_EINVAL null pointers, n_inputs outside 1..RIAB_FF_MAX_INPUTS, n_in < 1,
+ * n_out outside 1..RIAB_GP_MAX_OUT, n_train < 1, T < 0, B < 1, inv_two_ell2 not finite or <= 0; RIAB_ETOOBIG n_train >
+ * RIAB_GP_MAX_TRAIN or T * ceil(B / 128) >= 2^31; RIAB_EALIGN B % 4 or a pointer that is not 16-byte aligned. */
+#define RIAB_GP_MAX_TRAIN 16384
+#define RIAB_GP_MAX_OUT 4
+int riab_gp_predict(const RiabFFInput* inputs, int32_t n_inputs, const float* sq_train, const float* alpha, int32_t n_out,
+                    int32_t n_train, float inv_two_ell2, int64_t T, int64_t B, float* out, riab_stream_t stream);
 
 /* sizeof of the ABI's structs as compiled into the library (which: 0 RiabEnv, 1 RiabMotion, 2 RiabRateIO,
  * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer, 11 RiabMLPLayer, 12 RiabMomentInput; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at

@@ -533,6 +533,13 @@ class Neurons:
         from ._decoder import fit_linear_decoder
         return fit_linear_decoder([self], **kw)
 
+    def fit_gp_decoder(self, **kw):
+        """A Gaussian-process decoder (the reference's GaussianProcessRegressor with a fixed RBF kernel) from this
+        population's recorded rates to the agent's recorded target (`_gp_decoder.fit_gp_decoder([self], **kw)`: target="pos",
+        t_start, t_end, stride, alpha=0.01, length_scale=None, max_samples=4096, samples=None), fitted on the device."""
+        from ._gp_decoder import fit_gp_decoder
+        return fit_gp_decoder([self], **kw)
+
     def reset_history(self):
         if self.Agent._plan is not None:
             self.Agent._plan.close()  # (its open rows live in the chunks dropped here)

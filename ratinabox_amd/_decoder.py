@@ -100,7 +100,59 @@ def history_moments_tensor(populations, target="pos", t_start=None, t_end=None, 
     return M, layout
 
 
-class LinearDecoder:
+class HistoryDecoder:
+    """What every decoder fitted from the device history shares: the populations it reads, the trajectory rows it was
+    fitted to, and `decode` / `error` on top of the subclass's `decode_tensor`.  A subclass sets `target` and provides
+    `_populations()` (or raises: a decoder built from bare arrays has none) and `decode_tensor(t_start, t_end)` ->
+    float32 `[T][D][Bp]`."""
+
+    target = "pos"
+
+    def _populations(self):
+        raise NotImplementedError
+
+    def decode_tensor(self, t_start=None, t_end=None):
+        raise NotImplementedError
+
+    def _pieces_of_rates(self, t_start, t_end):
+        """(agent, [views of every population's rows, one list per piece lying in ONE chunk of each history])"""
+        pops = self._populations()
+        agent = pops[0].Agent
+        start, stop = _rows(agent, pops, t_start, t_end)
+        hists = [p._hist_fr for p in pops]
+        return agent, [[h.chunks[c][r:r + length] for h, (c, r) in zip(hists, first)]
+                       for first, length in history_pieces([h.filled for h in hists], start, stop, 1, _max_rows(agent._Bp))]
+
+    def _joined(self, agent, parts):
+        D = len(TARGETS[self.target])
+        if not parts:
+            return torch.empty((0, D, agent._Bp), dtype=torch.float32, device=agent._device)
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+    def decode(self, t_start=None, t_end=None):
+        """`decode_tensor` on the host: NumPy (T, B, D), or (T, D) for one agent."""
+        agent = self._populations()[0].Agent
+        a = self.decode_tensor(t_start, t_end)[:, :, :agent._B].permute(0, 2, 1).cpu().numpy()
+        return a[:, 0] if agent._B == 1 else a
+
+    def _target_tensor(self, t_start, t_end):
+        pops = self._populations()
+        agent = pops[0].Agent
+        start, stop = _rows(agent, pops, t_start, t_end)
+        h = agent._hist
+        rows = list(TARGETS[self.target])
+        parts = [h.chunks[c][r:r + length][:, rows] for ((c, r),), length in history_pieces([h.filled], start, stop)]
+        return self._joined(agent, parts)
+
+    def error(self, t_start=None, t_end=None):
+        """Mean Euclidean distance between the decoded and the recorded target over the rows, per agent: float64 (B,)
+        device tensor (rows whose target is not finite are left out of the mean)."""
+        agent = self._populations()[0].Agent
+        d = self.decode_tensor(t_start, t_end).to(torch.float64) - self._target_tensor(t_start, t_end).to(torch.float64)
+        return torch.sqrt((d * d).sum(dim=1))[:, :agent._B].nanmean(dim=0)
+
+
+class LinearDecoder(HistoryDecoder):
     """sklearn.linear_model.Ridge(alpha) with an intercept, solved from a moment matrix in float64 on its device:
     xbar = s / N, ybar = sum y / N, A = G - N xbar xbar^T + alpha I, W = A^-1 (C - N xbar ybar^T), b = ybar - xbar W.
     `coef_` (D, n) and `intercept_` (D,) are float64 tensors on the moments' device."""
@@ -150,42 +202,10 @@ class LinearDecoder:
     def decode_tensor(self, t_start=None, t_end=None):
         """The decoded target of the history rows `get_history_slice(t_start, t_end)` (both None: every row): float32
         `[T][D][Bp]` on the device, out[t][d][b] = sum_k coef_[d][k] rates[t][k][b] + intercept_[d]."""
-        pops = self._populations()
-        agent = pops[0].Agent
-        start, stop = _rows(agent, pops, t_start, t_end)
+        agent, pieces = self._pieces_of_rates(t_start, t_end)
         wts, bias = self._device_tables(agent._device)
-        hists = [p._hist_fr for p in pops]
-        parts = []
-        for first, length in history_pieces([h.filled for h in hists], start, stop, 1, _max_rows(agent._Bp)):
-            views = [h.chunks[c][r:r + length] for h, (c, r) in zip(hists, first)]
-            parts.append(torch.ops.riab.feedforward(views, wts, bias, _L.ACTIVATIONS["linear"], [0.0, 0.0, 0.0, 0.0]))
-        if not parts:
-            return torch.empty((0, self.layout.D, agent._Bp), dtype=torch.float32, device=agent._device)
-        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
-
-    def decode(self, t_start=None, t_end=None):
-        """`decode_tensor` on the host: NumPy (T, B, D), or (T, D) for one agent."""
-        agent = self._populations()[0].Agent
-        a = self.decode_tensor(t_start, t_end)[:, :, :agent._B].permute(0, 2, 1).cpu().numpy()
-        return a[:, 0] if agent._B == 1 else a
-
-    def _target_tensor(self, t_start, t_end):
-        pops = self._populations()
-        agent = pops[0].Agent
-        start, stop = _rows(agent, pops, t_start, t_end)
-        h = agent._hist
-        rows = list(self.layout.target_rows)
-        parts = [h.chunks[c][r:r + length][:, rows] for ((c, r),), length in history_pieces([h.filled], start, stop)]
-        if not parts:
-            return torch.empty((0, self.layout.D, agent._Bp), dtype=torch.float32, device=agent._device)
-        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
-
-    def error(self, t_start=None, t_end=None):
-        """Mean Euclidean distance between the decoded and the recorded target over the rows, per agent: float64 (B,)
-        device tensor (rows whose target is not finite are left out of the mean)."""
-        agent = self._populations()[0].Agent
-        d = self.decode_tensor(t_start, t_end).to(torch.float64) - self._target_tensor(t_start, t_end).to(torch.float64)
-        return torch.sqrt((d * d).sum(dim=1))[:, :agent._B].nanmean(dim=0)
+        return self._joined(agent, [torch.ops.riab.feedforward(views, wts, bias, _L.ACTIVATIONS["linear"], [0.0, 0.0, 0.0, 0.0])
+                                    for views in pieces])
 
     def as_layer(self, params={}):
         """The decoder as a live FeedForwardLayer (linear activation, n = D, the populations as inputs, `w` and `biases`

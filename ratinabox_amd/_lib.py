@@ -160,6 +160,7 @@ MLP_MAX_LAYERS, MLP_MAX_HIDDEN = 8, 128                                  # riab_
 WALL_GRID_MAX = 16                                                      # riab_hip.h RIAB_WALL_GRID_MAX
 RATEMAP_MAX_BINS, RATEMAP_DROPPED, RATEMAP_FP32_RUN = 4096, 0xFFFF, 0     # riab_hip.h RIAB_RATEMAP_*
 MOMENTS_MAX_TARGETS, MOMENTS_MAX_M = 4, 4096                            # riab_hip.h RIAB_MOMENTS_MAX_*
+GP_MAX_TRAIN, GP_MAX_OUT = 16384, 4                                     # riab_hip.h RIAB_GP_MAX_*
 CU_PROBE_WORDS = 4097                                                   # riab_hip.h RIAB_CU_PROBE_WORDS
 STEP1_MAIL_STRIDE = 1088                                                # riab_hip.h RIAB_STEP1_MAIL_STRIDE
 
@@ -266,6 +267,8 @@ PROTOTYPES = {
     "riab_history_moments": (C.c_int, [C.POINTER(RiabMomentInput), C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
                                        C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+    "riab_gp_predict": (C.c_int, [C.POINTER(RiabFFInput), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
+                                  C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "riab_fill": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "riab_plan_create": (C.c_void_p, [C.POINTER(RiabEnv), C.POINTER(RiabMotion), C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -16,6 +16,7 @@ Functional operators (return a new tensor)
     spikes                                                              uint8 (T, n, B) from rates (T, n, B)
     feedforward                                                         float32 (T, n_out, B)
     mlp_forward   a whole multi-layer perceptron in one launch (contribs.NeuralNetworkNeurons)   float32 (T, n_out, B)
+    gp_predict    the predictive mean of an RBF Gaussian-process decoder over rate rows                 float32 (T, D, B)
 In-place operators
     history_moments  the float64 moment matrix of [rates ; targets ; 1] over history rows: what a ridge decoder is solved from
     td_forward_tail  the tail of ValueNeuron.update(): dV/dt, V_last and (optionally) the eligibility traces
@@ -645,3 +646,41 @@ def history_moments(inputs: List[Tensor], traj: Tensor, target_rows: List[int], 
     _L.check(_L.lib.riab_history_moments(arr, len(inputs), _L.ptr(traj), rows, len(target_rows), T, int(t_step), B,
                                          int(n_real), _L.ptr(moments), _L.ptr(n_dropped), _L.ptr(ws), _L.current_stream()),
              "riab_history_moments")
+
+
+# ---- Gaussian-process decoders over history rows: riab_gp_predict -----------------------------------------------------
+@_register("gp_predict(Tensor[] inputs, Tensor[] train_t, Tensor sq_train, Tensor alpha, int n_train, float inv_two_ell2) "
+           "-> Tensor", lambda inputs, train_t, sq_train, alpha, n_train, inv_two_ell2:
+           inputs[0].new_empty((inputs[0].shape[0], alpha.shape[0], inputs[0].shape[2])))
+def gp_predict(inputs: List[Tensor], train_t: List[Tensor], sq_train: Tensor, alpha: Tensor, n_train: int,
+               inv_two_ell2: float) -> Tensor:
+    """The predictive mean of an RBF Gaussian process over rate rows (riab_gp_predict: fp32 matrix cores, exponential and
+    alpha contraction fused): out[t][d][b] = sum_{j < n_train} exp(-max(0, |x*|^2 + |x_j|^2 - 2 x*.x_j) inv_two_ell2)
+    alpha[d][j], x* the concatenated inputs_l[t, :, b].  inputs_l float32 (T, n_l, B); train_t_l float32 (n_l, Np): the
+    training matrix of input l TRANSPOSED, Np = n_train rounded up to 32, zero padded; sq_train float32 (Np,) = |x_j|^2;
+    alpha float32 (D, Np), D = 1..4, zero padded.  Returns float32 (T, D, B)."""
+    if not inputs or len(inputs) != len(train_t) or len(inputs) > 8:
+        raise ValueError("1..8 inputs, one transposed training matrix each")
+    T, _, B = (int(x) for x in inputs[0].shape)
+    n_train = int(n_train)
+    Np = (n_train + 31) // 32 * 32
+    dev = inputs[0].device
+    arr = (_L.RiabFFInput * len(inputs))()
+    for l, (x, w) in enumerate(zip(inputs, train_t)):
+        if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous() or x.shape[0] != T or x.shape[2] != B or \
+                x.device != dev:
+            raise ValueError("inputs must be contiguous float32 (T, n_l, B) with equal T, B and device")
+        if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous() or w.shape[0] != x.shape[1] or \
+                w.shape[1] != Np or w.device != dev:
+            raise ValueError(f"train_t[l] must be contiguous float32 (n_l, {Np}) on the inputs' device")
+        arr[l].rates, arr[l].wt, arr[l].n_in = x.data_ptr(), w.data_ptr(), int(x.shape[1])
+    if sq_train.dtype != torch.float32 or tuple(sq_train.shape) != (Np,) or not sq_train.is_contiguous() or sq_train.device != dev:
+        raise ValueError(f"sq_train must be a contiguous float32 tensor ({Np},) on the inputs' device")
+    if alpha.dtype != torch.float32 or alpha.dim() != 2 or alpha.shape[1] != Np or not alpha.is_contiguous() or \
+            alpha.device != dev:
+        raise ValueError(f"alpha must be a contiguous float32 tensor (D, {Np}) on the inputs' device")
+    D = int(alpha.shape[0])
+    out = torch.empty((T, D, B), dtype=torch.float32, device=dev)
+    _L.check(_L.lib.riab_gp_predict(arr, len(inputs), _L.ptr(sq_train), _L.ptr(alpha), D, n_train, float(inv_two_ell2), T, B,
+                                    _L.ptr(out), _L.current_stream()), "riab_gp_predict")
+    return out

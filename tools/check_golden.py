@@ -4,7 +4,9 @@ tests/golden/make_golden.py, tests/golden/make_golden_td.py (the TD learners' fi
 tests/golden/make_golden_theta.py (the phase-precessing place cells'; section name `theta`) and
 tests/golden/make_golden_subagent.py (contribs.SubAgent's; section name `subagent`) and
 tests/golden/make_golden_plane_wave.py (contribs.PlaneWaveNeurons'; section name `plane_wave`) and
-tests/golden/make_golden_decoder.py (the linear decoder's; section name `decoder`; needs scikit-learn) into a temporary directory and compare with the committed tests/golden/*.npz, array by
+tests/golden/make_golden_decoder.py (the linear decoder's; section name `decoder`; needs scikit-learn) and
+tests/golden/make_golden_gp_decoder.py (the Gaussian-process decoder's; section name `gp_decoder`; reads the committed
+decoder_reference.npz and needs scikit-learn only) into a temporary directory and compare with the committed tests/golden/*.npz, array by
 array, bit for bit.  Every section of the generator seeds its own noise stream, so `--sections a b` checks a subset
 just as well.
 
@@ -30,7 +32,7 @@ def main():
     ap.add_argument("--keep", action="store_true", help="keep the temporary directory")
     a = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="riab_golden_")
-    main_sections = [x for x in a.sections if x not in ("td", "theta", "subagent", "plane_wave", "decoder")]
+    main_sections = [x for x in a.sections if x not in ("td", "theta", "subagent", "plane_wave", "decoder", "gp_decoder")]
     cmds = []
     if main_sections or not a.sections:
         cmds.append([sys.executable, os.path.join(GOLDEN, "make_golden.py"), *main_sections, "--out", tmp])
@@ -44,6 +46,8 @@ def main():
         cmds.append([sys.executable, os.path.join(GOLDEN, "make_golden_plane_wave.py"), "--out", tmp])
     if "decoder" in a.sections or not a.sections:
         cmds.append([sys.executable, os.path.join(GOLDEN, "make_golden_decoder.py"), "--out", tmp])
+    if "gp_decoder" in a.sections or not a.sections:
+        cmds.append([sys.executable, os.path.join(GOLDEN, "make_golden_gp_decoder.py"), "--out", tmp])
     for cmd in cmds:
         subprocess.run(cmd, check=True, env=dict(os.environ, MPLBACKEND="Agg"), stdout=subprocess.DEVNULL)
     bad = 0
