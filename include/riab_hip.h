@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RIAB_ABI_VERSION 11    /* (the riab_history_* entry points, riab_history_moments among them, and riab_gp_predict were added at 11
+#define RIAB_ABI_VERSION 11    /* (the riab_history_* entry points, riab_history_moments and riab_history_window_counts among them, riab_gp_predict and riab_bayes_decode were added at 11
                                 * without a bump: they are new exports only; no struct, enum value or existing signature
                                 * changed, so an older binding still loads this library and a newer one finds a missing
                                 * export at load time) */
@@ -1385,6 +1385,51 @@ int riab_history_moments(const RiabMomentInput* inputs, int32_t n_inputs, const 
 #define RIAB_GP_MAX_OUT 4
 int riab_gp_predict(const RiabFFInput* inputs, int32_t n_inputs, const float* sq_train, const float* alpha, int32_t n_out,
                     int32_t n_train, float inv_two_ell2, int64_t T, int64_t B, float* out, riab_stream_t stream);
+
+/* ---- Bayesian (Poisson maximum-likelihood) position decoding from spikes on the device history ---------------------------
+ * The decoder of the place-cell literature: spike counts k_c of a time window of duration tau against the cells' tuning
+ * curves f_cj over J position bins with centres x_j.  The caller builds the tables (ratinabox_amd/_bayes_decoder.py):
+ * L_cj = log max(f_cj, floor) and bias_j = log prior_j - tau sum_c max(f_cj, floor), bias_j = -inf for a bin that is not
+ * admissible.  The log posterior is l_j = sum_c k_c L_cj + bias_j.  (New exports at ABI 11, like riab_gp_predict: no
+ * struct, enum value or existing signature changes.) */
+#define RIAB_BAYES_MAX_WINDOW 255      /* history rows per window: a uint8 count of 0 / 1 spikes cannot overflow */
+#define RIAB_BAYES_OUT_ROWS 6          /* mean x, mean y, MAP x, MAP y, log evidence, MAP probability */
+
+/* The counts of windows of `window` consecutive rows, piece by piece: rows device uint8 [T][n][B] is one piece of the spike
+ * history whose row r is selected row row0 + r and belongs to window (row0 + r) / window; counts device uint8
+ * [n_windows][n][B], ADDED to (zeroed by the caller before the first piece): counts[w][c][b] += rows[r][c][b].  Rows of
+ * windows >= n_windows are ignored.  Every byte is added on its own, modulo 256 (a padding lane may hold anything); each
+ * output byte has one owner thread, and the calls of one decode are ordered on the stream: no atomics.  T = 0 or
+ * n_windows = 0 launches nothing.  RIAB_EINVAL: null pointers, window outside 1..RIAB_BAYES_MAX_WINDOW, T < 0, n < 1,
+ * B < 1, row0 < 0, n_windows < 0; RIAB_EALIGN: B % 4 or a pointer that is not 4-byte aligned; RIAB_ETOOBIG: T * n * B / 4 >=
+ * 2^31 - 1 (split the rows). */
+int riab_history_window_counts(const uint8_t* rows, int64_t T, int32_t n, int64_t B, int64_t row0, int32_t window,
+                               int64_t n_windows, uint8_t* counts, riab_stream_t stream);
+
+/* The decode, one fused kernel: out[t][0..5][b] of every (window t, lane b) sample =
+ *   posterior mean  sum_j softmax(l)_j x_j (x, y);   MAP centre x_j* (x, y), j* the LOWEST j among the maxima of l;
+ *   log evidence    logsumexp_j l_j;                  MAP probability softmax(l)_j*.
+ * Six NaNs when no bin is admissible, or when l is not finite where it counts (a NaN rate): that sample alone.
+ *   inputs[l].rates  device [T][n_in][B]: uint8 counts (inputs_are_counts; 4-byte aligned) or float32 rates (16-byte
+ *                    aligned), which are multiplied by `scale` (= tau; ignored for counts)
+ *   inputs[l].wt     device float32 [n_in][Jp]: L of that population, wt[c][j]; Jp a multiple of 32, >= J (the padding
+ *                    columns j >= J are read and taken as 0, whatever they hold)
+ *   bias             device float32 [Jp]; entries j >= J are not read (such bins are inadmissible)
+ *   centres          device float32 [2][Jp]: x_j, then y_j
+ *   out              device float32 [T][RIAB_BAYES_OUT_ROWS][B]
+ *   block_tiles      0: the launcher chooses how many 32-bin tiles a block of bins has (4 at Jp >= 128, 2 at Jp >= 64,
+ *                    else 1); 1, 2 or 4 force it.  The results do not depend on it, bit for bit.
+ * The cross term runs on v_mfma_f32_32x32x2_f32 (exact fp32 accumulation, k ascending; integer counts are exact); the
+ * softmax is a running one over blocks of bins (v_exp_f32), so no T B x J intermediate reaches memory.  Positions are
+ * columns: whatever a padding lane holds stays in its own column.  Fixed order, no atomics, no workspace; the instruction
+ * sequence of a sample depends on neither T, B nor its place: a window decoded alone has the bits of the same window
+ * inside a many-window call.  T = 0 launches nothing.
+ * Checked before anything is launched: RIAB_EINVAL null pointers, n_inputs outside 1..RIAB_FF_MAX_INPUTS, n_in < 1, J < 1,
+ * Jp < J, T < 0, B < 1, block_tiles not one of 0, 1, 2, 4, a scale that is not finite (rates); RIAB_EUNSUPPORTED J >
+ * RIAB_RATEMAP_MAX_BINS; RIAB_EALIGN B % 4, Jp % 32 or a misaligned pointer; RIAB_ETOOBIG T * ceil(B / 128) >= 2^31. */
+int riab_bayes_decode(const RiabFFInput* inputs, int32_t n_inputs, int32_t inputs_are_counts, float scale,
+                      const float* bias, const float* centres, int32_t J, int32_t Jp, int64_t T, int64_t B, float* out,
+                      int32_t block_tiles, riab_stream_t stream);
 
 /* sizeof of the ABI's structs as compiled into the library (which: 0 RiabEnv, 1 RiabMotion, 2 RiabRateIO,
  * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer, 11 RiabMLPLayer, 12 RiabMomentInput; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at

@@ -540,6 +540,13 @@ class Neurons:
         from ._gp_decoder import fit_gp_decoder
         return fit_gp_decoder([self], **kw)
 
+    def fit_bayesian_decoder(self, **kw):
+        """A Bayesian (Poisson maximum-likelihood) decoder of position from this population's recorded SPIKES
+        (`_bayes_decoder.fit_bayesian_decoder([self], **kw)`: tuning="history", bin_size=0.05, t_start, t_end, spikes=False,
+        prior="uniform", rate_floor=1e-2, window=1), its tables built on the device."""
+        from ._bayes_decoder import fit_bayesian_decoder
+        return fit_bayesian_decoder([self], **kw)
+
     def reset_history(self):
         if self.Agent._plan is not None:
             self.Agent._plan.close()  # (its open rows live in the chunks dropped here)

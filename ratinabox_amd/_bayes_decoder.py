@@ -1,0 +1,250 @@
+"""Bayesian (Poisson maximum-likelihood) position decoding from spikes, fitted and run where the history lives.
+
+The decoder of the place-cell literature: the spike counts k_c of the cells in a time window of duration tau = W dt are set
+against the cells' tuning curves f_cj over J position bins with centres x_j, and under independent Poisson firing the log
+posterior of bin j is
+
+    l_j = sum_c k_c log max(f_cj, floor) + log prior_j - tau sum_c max(f_cj, floor)
+
+(`rate_floor` keeps a silent cell from vetoing a bin).  The tuning curves come from `_ratemap.rate_map_tensors` over the fit
+rows (tuning="history": rates, or spikes / dt) or from `get_state_tensor(evaluate_at="all")` on the environment's own grid
+(tuning="groundtruth"); the tables are built in float64 with torch on the device and stored as float32.  The decode walks
+the spike history's chunks: windows of W > 1 rows are counted by `torch.ops.riab.history_window_counts` across chunk
+boundaries, and every (window, agent) sample goes through `torch.ops.riab.bayes_decode` (csrc/riab_bayes.hip): one fused
+kernel on the fp32 matrix cores with a running softmax that never writes the (samples x J) log posterior to memory.  Per
+sample it returns the posterior mean, the MAP bin's centre, the log evidence and the MAP probability."""
+import numpy as np
+import torch
+
+from . import _lib as _L
+from . import ops as _ops  # noqa: F401  (registers torch.ops.riab.bayes_decode / history_window_counts)
+from . import utils
+from ._decoder import MAX_POPULATIONS, HistoryDecoder, _check_populations, _max_rows, _rows
+from ._ratemap import history_pieces, rate_map_tensors
+
+MAX_BINS = _L.RATEMAP_MAX_BINS
+MAX_WINDOW = _L.BAYES_MAX_WINDOW
+OUT_ROWS = {"mean": (0, 1), "map": (2, 3), "log_evidence": (4,), "map_probability": (5,)}
+
+
+def window_pieces(filled, start, stop, window, max_rows=None):
+    """The windows of `window` consecutive rows of [start, stop) over several histories of the same steps: (n_windows,
+    [(first rows, length, row0)]) where the pieces are `history_pieces` of the rows [start, start + n_windows window) —
+    each lies in ONE chunk of every history — and `row0` is the piece's first row counted from `start`, so that its row r
+    belongs to window (row0 + r) // window.  Trailing rows that do not fill a window are dropped."""
+    start, stop, window = int(start), int(stop), int(window)
+    if not 1 <= window <= MAX_WINDOW:
+        raise ValueError(f"window must be 1..{MAX_WINDOW} rows, got {window}")
+    n_windows = max(0, stop - start) // window
+    end = start + n_windows * window
+    out, g = [], start
+    for first, length in (history_pieces(filled, start, end, 1, max_rows) if n_windows else []):
+        out.append((first, length, g - start))
+        g += length
+    return n_windows, out
+
+
+def window_centre_rows(start, n_windows, window):
+    """The history row at the centre of every window: start + w window + window // 2, an int64 array."""
+    return int(start) + np.arange(int(n_windows), dtype=np.int64) * int(window) + int(window) // 2
+
+
+def grid_centres(extent, dx):
+    """Bin centres float64 (2, ny nx) of the maps `rate_map_tensors` returns over `extent` at bins `dx` wide, from the same
+    edges and in the maps' flattening: row-major over (ny, nx) with the first row the TOP of the room.  -> (centres, ny, nx)"""
+    ex, ey = utils.histogram_bin_edges(extent, dx)
+    nx, ny = len(ex) - 1, len(ey) - 1
+    if nx < 1 or ny < 1:
+        raise ValueError("the grid has no bins")
+    cx, cy = 0.5 * (ex[:-1] + ex[1:]), 0.5 * (ey[:-1] + ey[1:])
+    return np.stack((np.tile(cx, ny), np.repeat(cy[::-1], nx))), ny, nx
+
+
+class BayesianDecoder(HistoryDecoder):
+    """A fitted Poisson maximum-likelihood decoder.  `log_rates`: one float32 (n_l, Jp) table log max(f, floor) per
+    population; `S` float32 (Jp,) = sum_c max(f_cj, floor); `log_prior` float32 (Jp,), -inf for a bin that is not admissible
+    (never visited, or padding); `centres` float32 (2, Jp); Jp = `n_bins` rounded up to 32.  All on the fit's device."""
+
+    target = "pos"
+
+    def __init__(self, log_rates, S, log_prior, centres, n_bins, dt, window=1, populations=None, grid_shape=None,
+                 tuning="history", prior="uniform", rate_floor=1e-2):
+        self.log_rates, self.S, self.log_prior, self.centres = list(log_rates), S, log_prior, centres
+        self.n_bins, self.dt = int(n_bins), float(dt)
+        self.widths = [int(t.shape[0]) for t in self.log_rates]
+        self.window = _check_window(window)
+        self.populations = None if populations is None else list(populations)
+        self.grid_shape, self.tuning, self.prior, self.rate_floor = grid_shape, tuning, prior, float(rate_floor)
+
+    @classmethod
+    def from_tuning(cls, tuning_curves, centres, dt, admissible=None, prior_weights=None, rate_floor=1e-2, **kw):
+        """The tables from bare tuning curves: a list of float64 (n_l, J) tensors (Hz) on one device, `centres` float64
+        (2, J), `admissible` bool (J,) or None (every bin), `prior_weights` float64 (J,) of non-negative weights or None
+        (uniform over the admissible bins); the prior is normalised here."""
+        tuning_curves = list(tuning_curves)
+        if not 1 <= len(tuning_curves) <= MAX_POPULATIONS:
+            raise ValueError(f"a decoder takes 1..{MAX_POPULATIONS} populations, got {len(tuning_curves)}")
+        dev = tuning_curves[0].device
+        J = int(tuning_curves[0].shape[1])
+        if not 1 <= J <= MAX_BINS:
+            raise ValueError(f"a Bayesian decoder takes 1..{MAX_BINS} position bins, got {J}: use larger bins")
+        if not float(rate_floor) > 0:
+            raise ValueError(f"rate_floor must be positive, got {rate_floor}")
+        Jp = (J + 31) // 32 * 32
+        ok = torch.ones(J, dtype=torch.bool, device=dev) if admissible is None else admissible.to(dev).reshape(J).bool()
+        w = ok.to(torch.float64)
+        if prior_weights is not None:
+            w = w * prior_weights.to(dev).reshape(J).to(torch.float64)
+        logp = torch.full((Jp,), -float("inf"), dtype=torch.float64, device=dev)
+        logp[:J] = torch.where(w > 0, torch.log(w / w.sum()), -float("inf"))
+        S = torch.zeros(Jp, dtype=torch.float64, device=dev)
+        tables = []
+        for f in tuning_curves:
+            if f.dtype != torch.float64 or f.dim() != 2 or int(f.shape[1]) != J or f.device != dev:
+                raise ValueError("tuning curves must be float64 tensors (n_l, J) on one device")
+            F = f.clamp(min=float(rate_floor))
+            S[:J] += F.sum(dim=0)
+            L = torch.zeros((int(f.shape[0]), Jp), dtype=torch.float32, device=dev)
+            L[:, :J] = torch.log(F).to(torch.float32)
+            tables.append(L)
+        c = torch.zeros((2, Jp), dtype=torch.float32, device=dev)
+        c[:, :J] = centres.to(dev).to(torch.float32)
+        return cls(tables, S.to(torch.float32), logp.to(torch.float32), c, J, dt, rate_floor=rate_floor, **kw)
+
+    def bias(self, window=None):
+        """bias_j = log prior_j - tau S_j of windows of `window` rows (tau = window dt), float32 (Jp,): formed in float64
+        from the stored float32 tables."""
+        tau = _check_window(self.window if window is None else window) * self.dt
+        return (self.log_prior.to(torch.float64) - tau * self.S.to(torch.float64)).to(torch.float32)
+
+    # ---- running the decoder ------------------------------------------------------------------------------------------
+    def _populations(self):
+        if self.populations is None:
+            raise ValueError("this decoder was built from bare tuning curves: it has no populations to read spikes from")
+        return self.populations
+
+    def decode_inputs_tensor(self, inputs, window=1, block_tiles=0):
+        """The six output rows of inputs that are not in a history: a list of uint8 count tensors or float32 rate tensors
+        `[T][n_l][Bp]`, one per population, each sample a window of `window` rows' duration -> float32 `[T][6][Bp]`."""
+        inputs = list(inputs)
+        if len(inputs) != len(self.widths) or any(int(x.shape[1]) != w for x, w in zip(inputs, self.widths)):
+            raise ValueError(f"this decoder takes {len(self.widths)} input tensors (T, n_l, Bp) of widths {self.widths}")
+        tau = _check_window(window) * self.dt
+        return torch.ops.riab.bayes_decode(inputs, self.log_rates, self.bias(window), self.centres, self.n_bins, tau,
+                                           int(block_tiles))
+
+    def _windows(self, t_start, t_end, window, inputs):
+        """(agent, histories read, start, window, n_windows, pieces) of a decode"""
+        window = _check_window(self.window if window is None else window)
+        if inputs not in ("spikes", "rates"):
+            raise ValueError(f"inputs must be 'spikes' or 'rates', got {inputs!r}")
+        if inputs == "rates" and window != 1:
+            raise ValueError("inputs='rates' decodes single rows (k = dt * rate): window must be 1")
+        pops = self._populations()
+        agent = pops[0].Agent
+        start, stop = _rows(agent, pops, t_start, t_end)
+        hists = [_spike_history(p, stop) for p in pops] if inputs == "spikes" else [p._hist_fr for p in pops]
+        n_windows, pieces = window_pieces([h.filled for h in hists], start, stop, window, _max_rows(agent._Bp))
+        return agent, hists, start, window, n_windows, pieces
+
+    def decode_all_tensor(self, t_start=None, t_end=None, window=None, inputs="spikes"):
+        """Every output of the windows of `window` (None: the fitted one) consecutive rows of the history rows
+        `get_history_slice(t_start, t_end)` (both None: every row), trailing rows that do not fill a window dropped:
+        float32 `[T'][6][Bp]` on the device, rows = posterior mean x, y; MAP centre x, y; log evidence; MAP probability.
+        inputs="spikes": the recorded spikes, counted per window; "rates": k = dt * rate of single rows (window 1)."""
+        agent, hists, _start, window, n_windows, pieces = self._windows(t_start, t_end, window, inputs)
+        if n_windows == 0:
+            return torch.empty((0, _L.BAYES_OUT_ROWS, agent._Bp), dtype=torch.float32, device=agent._device)
+        if window == 1:      # the rows are the samples: read in place
+            parts = [self.decode_inputs_tensor([h.chunks[c][r:r + length] for h, (c, r) in zip(hists, first)], 1)
+                     for first, length, _row0 in pieces]
+            return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+        counts = [torch.zeros((n_windows, w, agent._Bp), dtype=torch.uint8, device=agent._device) for w in self.widths]
+        for first, length, row0 in pieces:
+            for h, (c, r), cnt in zip(hists, first, counts):
+                torch.ops.riab.history_window_counts(h.chunks[c][r:r + length], row0, window, cnt)
+        step = _max_rows(agent._Bp)
+        parts = [self.decode_inputs_tensor([cnt[o:o + step] for cnt in counts], window) for o in range(0, n_windows, step)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+    def decode_tensor(self, t_start=None, t_end=None, window=None, inputs="spikes", estimate="mean"):
+        """The decoded position of every window: float32 `[T'][2][Bp]`, the posterior mean (estimate="mean") or the MAP
+        bin's centre ("map")."""
+        if estimate not in ("mean", "map"):
+            raise ValueError(f"estimate must be 'mean' or 'map', got {estimate!r}")
+        lo = OUT_ROWS[estimate][0]
+        return self.decode_all_tensor(t_start, t_end, window, inputs)[:, lo:lo + 2]
+
+    def _target_tensor(self, t_start, t_end):
+        """The recorded position at the centre row of every window (of the fitted `window`)."""
+        pops = self._populations()
+        agent, window = pops[0].Agent, self.window
+        start, stop = _rows(agent, pops, t_start, t_end)
+        n_windows = (stop - start) // window
+        h = agent._hist
+        rows = [_L.H_POS_X, _L.H_POS_Y]
+        if n_windows == 0:
+            return self._joined(agent, [])
+        first_row = int(window_centre_rows(start, n_windows, window)[0])
+        parts = [h.chunks[c][r:r + length:window][:, rows]
+                 for ((c, r),), length in history_pieces([h.filled], first_row, start + n_windows * window, window)]
+        return self._joined(agent, parts)
+
+
+def _check_window(window):
+    if isinstance(window, bool) or int(window) != window or not 1 <= int(window) <= MAX_WINDOW:
+        raise ValueError(f"window must be an integer in 1..{MAX_WINDOW} rows, got {window}")
+    return int(window)
+
+
+def _spike_history(p, stop):
+    if not p.save_spikes or len(p._hist_sp) == 0:
+        raise ValueError(f"{p.name}: no recorded spikes to decode from (update() with save_history and save_spikes on "
+                         "fills the spike history)")
+    if stop > len(p._hist_sp):
+        raise ValueError(f"rows up to {stop} asked for, but {p.name}'s spike history has {len(p._hist_sp)} rows")
+    return p._hist_sp
+
+
+def fit_bayesian_decoder(populations, tuning="history", bin_size=0.05, t_start=None, t_end=None, spikes=False,
+                         prior="uniform", rate_floor=1e-2, window=1):
+    """A `BayesianDecoder` of the populations (1..8, of one Agent).  tuning="history": the tuning curves are the rate maps of
+    the rows `get_history_slice(t_start, t_end)` (both None: every row) at bins `bin_size` wide — of the recorded rates, or
+    with spikes=True of the recorded spikes divided by dt — and a bin never visited is not admissible.  tuning="groundtruth":
+    `get_state_tensor(evaluate_at="all")` on the environment's own grid (Environment.dx; `bin_size` is not used), every bin
+    admissible.  prior: "uniform" over the admissible bins or "occupancy" (the visits per bin; history tuning only).
+    `rate_floor` (Hz): the least rate a tuning curve is given.  `window`: the rows per decoding window (1..255)."""
+    if tuning not in ("history", "groundtruth"):
+        raise ValueError(f"tuning must be 'history' or 'groundtruth', got {tuning!r}")
+    if prior not in ("uniform", "occupancy"):
+        raise ValueError(f"prior must be 'uniform' or 'occupancy', got {prior!r}")
+    if prior == "occupancy" and tuning != "history":
+        raise ValueError("prior='occupancy' needs tuning='history': ground-truth tuning has no visits to count")
+    if not float(rate_floor) > 0:
+        raise ValueError(f"rate_floor must be positive, got {rate_floor}")
+    window = _check_window(window)
+    populations, agent = _check_populations(populations)
+    dev, dt = agent._device, float(agent.dt)
+    if tuning == "groundtruth":
+        env = agent.Environment
+        shape = tuple(int(s) for s in env.discrete_coords.shape[:2])
+        J = shape[0] * shape[1]
+        if J > MAX_BINS:
+            raise ValueError(f"the environment's grid has {J} bins, a Bayesian decoder takes 1..{MAX_BINS}: use a larger dx")
+        curves = [p.get_state_tensor(evaluate_at="all")[:, :J].to(torch.float64) for p in populations]
+        centres = torch.from_numpy(np.ascontiguousarray(np.asarray(env.flattened_discrete_coords, dtype=np.float64).T))
+        return BayesianDecoder.from_tuning(curves, centres, dt, rate_floor=rate_floor, window=window, populations=populations,
+                                           grid_shape=shape, tuning=tuning, prior=prior)
+    centres, ny, nx = grid_centres(agent.Environment.extent, bin_size)
+    if ny * nx > MAX_BINS:
+        raise ValueError(f"bins of {bin_size} make a grid of {ny * nx} bins, a Bayesian decoder takes 1..{MAX_BINS}: use larger bins")
+    start, stop = _rows(agent, populations, t_start, t_end)
+    curves, zero, visits = [], None, None
+    for p in populations:
+        hist = _spike_history(p, stop) if spikes else p._hist_fr
+        maps, zero, visits = rate_map_tensors(agent, hist, int(p.n), bin_size, start, stop, True)
+        curves.append((maps / dt if spikes else maps).reshape(int(p.n), ny * nx))
+    return BayesianDecoder.from_tuning(curves, torch.from_numpy(centres), dt, admissible=~zero.reshape(-1),
+                                       prior_weights=visits.reshape(-1) if prior == "occupancy" else None,
+                                       rate_floor=rate_floor, window=window, populations=populations, grid_shape=(ny, nx),
+                                       tuning=tuning, prior=prior)

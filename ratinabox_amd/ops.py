@@ -17,7 +17,9 @@ Functional operators (return a new tensor)
     feedforward                                                         float32 (T, n_out, B)
     mlp_forward   a whole multi-layer perceptron in one launch (contribs.NeuralNetworkNeurons)   float32 (T, n_out, B)
     gp_predict    the predictive mean of an RBF Gaussian-process decoder over rate rows                 float32 (T, D, B)
+    bayes_decode  Poisson maximum-likelihood position decoding of spike counts (or rates) over bins       float32 (T, 6, B)
 In-place operators
+    history_window_counts  spike rows of a history piece added into the uint8 counts of their time windows
     history_moments  the float64 moment matrix of [rates ; targets ; 1] over history rows: what a ridge decoder is solved from
     td_forward_tail  the tail of ValueNeuron.update(): dV/dt, V_last and (optionally) the eligibility traces
     td_update        ValueNeuron.update_weights(reward): TD error, batch-mean gradient on the matrix cores, W^T updated
@@ -683,4 +685,59 @@ def gp_predict(inputs: List[Tensor], train_t: List[Tensor], sq_train: Tensor, al
     out = torch.empty((T, D, B), dtype=torch.float32, device=dev)
     _L.check(_L.lib.riab_gp_predict(arr, len(inputs), _L.ptr(sq_train), _L.ptr(alpha), D, n_train, float(inv_two_ell2), T, B,
                                     _L.ptr(out), _L.current_stream()), "riab_gp_predict")
+    return out
+
+
+# ---- Bayesian decoding from spikes: riab_history_window_counts, riab_bayes_decode --------------------------------------
+@_register("history_window_counts(Tensor rows, int row0, int window, Tensor(a!) counts) -> ()",
+           lambda rows, row0, window, counts: None)
+def history_window_counts(rows: Tensor, row0: int, window: int, counts: Tensor) -> None:
+    """The spike counts of windows of `window` consecutive history rows (riab_history_window_counts), in place, piece by
+    piece: counts[(row0 + r) // window] += rows[r].  rows: uint8 (T, n, B), one piece of a spike history whose first row
+    is selected row `row0`; counts: uint8 (n_windows, n, B), ADDED to (rows of windows >= n_windows are ignored)."""
+    if rows.dtype != torch.uint8 or rows.dim() != 3 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous uint8 tensor (T, n, B)")
+    T, n, B = (int(x) for x in rows.shape)
+    if counts.dtype != torch.uint8 or counts.dim() != 3 or tuple(counts.shape[1:]) != (n, B) or not counts.is_contiguous() \
+            or counts.device != rows.device:
+        raise ValueError(f"counts must be a contiguous uint8 tensor (n_windows, {n}, {B}) on the rows' device")
+    _L.check(_L.lib.riab_history_window_counts(_L.ptr(rows), T, n, B, int(row0), int(window), int(counts.shape[0]),
+                                               _L.ptr(counts), _L.current_stream()), "riab_history_window_counts")
+
+
+@_register("bayes_decode(Tensor[] inputs, Tensor[] log_rates, Tensor bias, Tensor centres, int n_bins, float scale, "
+           "int block_tiles=0) -> Tensor", lambda inputs, log_rates, bias, centres, n_bins, scale, block_tiles=0:
+           bias.new_empty((inputs[0].shape[0], 6, inputs[0].shape[2])))
+def bayes_decode(inputs: List[Tensor], log_rates: List[Tensor], bias: Tensor, centres: Tensor, n_bins: int, scale: float,
+                 block_tiles: int = 0) -> Tensor:
+    """Poisson maximum-likelihood decoding of every (window, lane) sample (riab_bayes_decode: fp32 matrix cores, bias and
+    running softmax fused): l_j = sum_c k_c log_rates[c][j] + bias[j] over the bins j < n_bins, out[t, :, b] = (posterior
+    mean x, y; MAP centre x, y — the lowest j among the maxima —; logsumexp l; softmax(l) at the MAP bin), six NaNs where
+    no bin has a finite bias.  inputs_l: uint8 counts (T, n_l, B), or float32 rates (T, n_l, B) which are multiplied by
+    `scale` (the window's duration); log_rates_l float32 (n_l, Jp), Jp a multiple of 32 >= n_bins; bias float32 (Jp,), -inf
+    for a bin that is not admissible; centres float32 (2, Jp).  block_tiles: 0, or 1 / 2 / 4 to force the number of 32-bin
+    tiles per block (the results do not depend on it).  Returns float32 (T, 6, B)."""
+    if not inputs or len(inputs) != len(log_rates) or len(inputs) > 8:
+        raise ValueError("1..8 inputs, one log-rate table each")
+    T, _, B = (int(x) for x in inputs[0].shape)
+    dev, dtype = inputs[0].device, inputs[0].dtype
+    if dtype not in (torch.uint8, torch.float32):
+        raise ValueError("inputs must be uint8 counts or float32 rates")
+    if bias.dtype != torch.float32 or bias.dim() != 1 or not bias.is_contiguous() or bias.device != dev:
+        raise ValueError("bias must be a contiguous float32 tensor (Jp,) on the inputs' device")
+    Jp = int(bias.shape[0])
+    arr = (_L.RiabFFInput * len(inputs))()
+    for l, (x, w) in enumerate(zip(inputs, log_rates)):
+        if x.dtype != dtype or x.dim() != 3 or not x.is_contiguous() or x.shape[0] != T or x.shape[2] != B or x.device != dev:
+            raise ValueError("inputs must be contiguous (T, n_l, B) tensors of one dtype with equal T, B and device")
+        if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous() or w.shape[0] != x.shape[1] or \
+                w.shape[1] != Jp or w.device != dev:
+            raise ValueError(f"log_rates[l] must be contiguous float32 (n_l, {Jp}) on the inputs' device")
+        arr[l].rates, arr[l].wt, arr[l].n_in = x.data_ptr(), w.data_ptr(), int(x.shape[1])
+    if centres.dtype != torch.float32 or tuple(centres.shape) != (2, Jp) or not centres.is_contiguous() or centres.device != dev:
+        raise ValueError(f"centres must be a contiguous float32 tensor (2, {Jp}) on the inputs' device")
+    out = torch.empty((T, _L.BAYES_OUT_ROWS, B), dtype=torch.float32, device=dev)
+    _L.check(_L.lib.riab_bayes_decode(arr, len(inputs), 1 if dtype == torch.uint8 else 0, float(scale), _L.ptr(bias),
+                                      _L.ptr(centres), int(n_bins), Jp, T, B, _L.ptr(out), int(block_tiles),
+                                      _L.current_stream()), "riab_bayes_decode")
     return out
