@@ -1431,6 +1431,44 @@ int riab_bayes_decode(const RiabFFInput* inputs, int32_t n_inputs, int32_t input
                       const float* bias, const float* centres, int32_t J, int32_t Jp, int64_t T, int64_t B, float* out,
                       int32_t block_tiles, riab_stream_t stream);
 
+/* ---- The same decoder with a continuity prior, run as a causal forward filter over consecutive windows --------------------
+ * (csrc/riab_bayes_filter.hip; a new export at ABI 11: no struct, enum value or existing signature changes.)
+ * The bins lie on a grid (ny, nx), ny nx = J, flattened row-major; ok_j: prior_j > 0 <=> inv_norm_j > 0.  With Gaussian taps
+ * g[d], d = -radius..radius, g[-d] = g[d], that sum to 1, and G(r, c) = g[r] g[c] (taps that leave the grid are dropped):
+ *   q(j')   = p_{t-1}(j') inv_norm_j'         inv_norm_j' = 1 / sum_j G(j - j') ok_j, 0 where j' is not admissible
+ *   pred(j) = (1 - mixing) ok_j sum_j' G(j - j') q(j') + mixing prior_j
+ *   l_t(j)  = loglik[t][j] + log pred(j)      p_t = softmax(l_t)
+ * pred = prior on window 0 of a call with first != 0, on a window whose restart flag is set, and on the window after one
+ * whose column came out as six NaNs.  out[t] holds riab_bayes_decode's six rows of l_t; row 4, logsumexp l_t, is the
+ * predictive log likelihood log p(k_t | k_<t).
+ *   loglik      device float32 [W][Jp][B]: sum_c k_c L_cj - tau S_j of every window, -inf in a bin that is not admissible
+ *               (what riab_feedforward stores with bias -tau S, linear activation, n_out = Jp); bins j >= J are not read
+ *   taps        HOST float32 [radius + 1]: g[0..radius], each in [0, 1]
+ *   prior       device float32 [Jp]: the prior's probabilities, 0 in a bin that is not admissible (and in j >= J)
+ *   inv_norm    device float32 [Jp]
+ *   centres     device float32 [2][Jp]
+ *   restart     device uint8 [W][B] (non-zero: that column starts afresh at that window) or NULL
+ *   first       non-zero: a new run (post, tmp and the flags hold nothing); 0: continue the run the last call left there
+ *   post, tmp   device float32 [Jp][B] each: l of the last window, and the x-blur of q; the state between calls
+ *   workspace   device, RIAB_BAYES_FILTER_WORKSPACE_FLOATS(Jp, B) float32: S partial softmax states [S][5][B] followed
+ *               by one 32-bit "bad" flag per column, S = RIAB_BAYES_FILTER_SPLITS(Jp); part of the state between calls
+ *   out         device float32 [W][RIAB_BAYES_OUT_ROWS][B]
+ * 2 W launches in order on the stream (filter_post_kernel, filter_blur_kernel per window).  Fixed order, no atomics; the
+ * split of the bins depends on Jp alone and columns are independent: a column's bits depend on neither B nor its
+ * neighbours, and a call of W windows has the bits of W calls of one window.  Padding bins j >= J of post / tmp are written
+ * (-inf / 0).  W = 0 launches nothing.
+ * Checked before anything is launched: RIAB_EINVAL null pointers (restart may be NULL), W < 0, J < 1, Jp < J, ny nx != J,
+ * B < 1, radius outside 1..RIAB_BAYES_FILTER_MAX_RADIUS, mixing outside (0, 1], a tap outside [0, 1]; RIAB_EUNSUPPORTED
+ * J > RIAB_RATEMAP_MAX_BINS; RIAB_EALIGN B % 4, Jp % 32 or a pointer that is not 16-byte aligned (restart: any);
+ * RIAB_ETOOBIG W > 65535 or ceil(B / 64) >= 2^31. */
+#define RIAB_BAYES_FILTER_MAX_RADIUS 16
+#define RIAB_BAYES_FILTER_SPLITS(Jp) ((Jp) <= 512 ? (Jp) / 32 : ((Jp) + 127) / 128)
+#define RIAB_BAYES_FILTER_WORKSPACE_FLOATS(Jp, B) ((5 * (int64_t)RIAB_BAYES_FILTER_SPLITS(Jp) + 1) * (int64_t)(B))
+int riab_bayes_filter(const float* loglik, int64_t W, int32_t J, int32_t Jp, int32_t ny, int32_t nx, int64_t B,
+                      int32_t radius, const float* taps, float mixing, const float* prior, const float* inv_norm,
+                      const float* centres, const uint8_t* restart, int32_t first, float* post, float* tmp,
+                      float* workspace, float* out, riab_stream_t stream);
+
 /* sizeof of the ABI's structs as compiled into the library (which: 0 RiabEnv, 1 RiabMotion, 2 RiabRateIO,
  * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer, 11 RiabMLPLayer, 12 RiabMomentInput; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at
  * load */

@@ -12,7 +12,12 @@ rows (tuning="history": rates, or spikes / dt) or from `get_state_tensor(evaluat
 the spike history's chunks: windows of W > 1 rows are counted by `torch.ops.riab.history_window_counts` across chunk
 boundaries, and every (window, agent) sample goes through `torch.ops.riab.bayes_decode` (csrc/riab_bayes.hip): one fused
 kernel on the fp32 matrix cores with a running softmax that never writes the (samples x J) log posterior to memory.  Per
-sample it returns the posterior mean, the MAP bin's centre, the log evidence and the MAP probability."""
+sample it returns the posterior mean, the MAP bin's centre, the log evidence and the MAP probability.
+
+`BayesianDecoder.with_continuity()` adds the continuity prior of the literature (Zhang et al. 1998): `BayesianFilter` carries
+the posterior of a window to the next through a Gaussian step over the admissible bins, as a causal forward filter.  The
+likelihood of a batch of windows is `torch.ops.riab.feedforward` on the same tables, the scan over the windows
+`torch.ops.riab.bayes_filter` (csrc/riab_bayes_filter.hip): two kernels per window issued by one native call."""
 import numpy as np
 import torch
 
@@ -68,13 +73,14 @@ class BayesianDecoder(HistoryDecoder):
     target = "pos"
 
     def __init__(self, log_rates, S, log_prior, centres, n_bins, dt, window=1, populations=None, grid_shape=None,
-                 tuning="history", prior="uniform", rate_floor=1e-2):
+                 tuning="history", prior="uniform", rate_floor=1e-2, bin_width=None):
         self.log_rates, self.S, self.log_prior, self.centres = list(log_rates), S, log_prior, centres
         self.n_bins, self.dt = int(n_bins), float(dt)
         self.widths = [int(t.shape[0]) for t in self.log_rates]
         self.window = _check_window(window)
         self.populations = None if populations is None else list(populations)
         self.grid_shape, self.tuning, self.prior, self.rate_floor = grid_shape, tuning, prior, float(rate_floor)
+        self.bin_width = None if bin_width is None else float(bin_width)   # the side of the (square) bins at fit time
 
     @classmethod
     def from_tuning(cls, tuning_curves, centres, dt, admissible=None, prior_weights=None, rate_floor=1e-2, **kw):
@@ -191,6 +197,168 @@ class BayesianDecoder(HistoryDecoder):
         return self._joined(agent, parts)
 
 
+    def with_continuity(self, sigma=None, mixing=1e-3):
+        """This decoder with a continuity prior (`BayesianFilter`): the posterior of a window is carried to the next through
+        a Gaussian step of standard deviation `sigma` (m; None: agent.speed_mean x window x dt, floored at half a bin) over
+        the admissible bins, mixed with a share `mixing` in (0, 1] of the fitted prior."""
+        return BayesianFilter(self, sigma, mixing)
+
+
+FILTER_MAX_RADIUS = _L.BAYES_FILTER_MAX_RADIUS
+FILTER_LOGLIK_BYTES = 1 << 28     # the (windows, Jp, Bp) float32 log likelihood of one native call stays under this
+
+
+def continuity_taps(sigma, dx):
+    """(R, g): R = max(1, ceil(3 sigma / dx)) and the taps g[d] ~ exp(-(d dx)^2 / (2 sigma^2)), d = -R..R, float64 (2R + 1,)
+    normalised to sum 1.  ValueError for sigma <= 0 and for R > 16 (the step is not truncated silently)."""
+    sigma, dx = float(sigma), float(dx)
+    if not (sigma > 0 and np.isfinite(sigma)):
+        raise ValueError(f"sigma must be positive and finite, got {sigma}")
+    if not dx > 0:
+        raise ValueError(f"the bin width must be positive, got {dx}")
+    R = max(1, int(np.ceil(3.0 * sigma / dx)))
+    if R > FILTER_MAX_RADIUS:
+        raise ValueError(f"sigma = {sigma} m reaches over {R} bins of width {dx} m, the filter takes {FILTER_MAX_RADIUS}: use a "
+                         "smaller sigma or larger bins")
+    d = np.arange(-R, R + 1, dtype=np.float64) * dx
+    g = np.exp(-d * d / (2.0 * sigma * sigma))
+    return R, g / g.sum()
+
+
+class BayesianFilter(HistoryDecoder):
+    """A `BayesianDecoder` with a continuity prior, run as a causal forward filter over consecutive windows (the two-step
+    reconstruction of Zhang et al. 1998).  With p_{t-1} the posterior of the window before,
+
+        pred_t(j) = (1 - mixing) ok_j sum_j' G(j - j') p_{t-1}(j') / norm_j' + mixing prior_j
+        l_t(j)    = sum_c k_c L_cj - tau S_j + log pred_t(j)
+
+    where G is a separable Gaussian step of `radius` bins either way restricted to the admissible bins and normalised per
+    source bin (norm_j' = sum_j G(j - j') ok_j); pred = prior on the first window of a call, on a restarted window and after
+    a window that came out as NaN.  `taps` float64 (2 radius + 1,); `prior`, `inv_norm` float32 (Jp,) on the device."""
+
+    target = "pos"
+
+    def __init__(self, decoder, sigma=None, mixing=1e-3):
+        if decoder.grid_shape is None or decoder.bin_width is None:
+            raise ValueError("a continuity prior needs the decoder's grid (grid_shape and bin_width): a decoder built from bare "
+                             "tuning curves has none")
+        ny, nx = (int(v) for v in decoder.grid_shape)
+        if ny * nx != decoder.n_bins:
+            raise ValueError(f"the grid {ny} x {nx} does not hold the decoder's {decoder.n_bins} bins")
+        if not 0.0 < float(mixing) <= 1.0:
+            raise ValueError(f"mixing must lie in (0, 1], got {mixing}")
+        dx = decoder.bin_width
+        if sigma is None:
+            agent = decoder._populations()[0].Agent
+            sigma = max(float(agent.speed_mean) * decoder.window * decoder.dt, 0.5 * dx)
+        self.radius, self.taps = continuity_taps(sigma, dx)
+        self.decoder, self.sigma, self.mixing, self.grid_shape = decoder, float(sigma), float(mixing), (ny, nx)
+        self.window = decoder.window
+        J, Jp, dev, R = decoder.n_bins, int(decoder.S.shape[0]), decoder.S.device, self.radius
+        logp = decoder.log_prior.to(torch.float64)
+        ok = torch.isfinite(logp[:J]).reshape(ny, nx)
+        g = torch.from_numpy(self.taps).to(dev)
+        # norm_j' = sum_j G(j - j') ok_j: the two blurs of the mask, taps that leave the grid dropped
+        along_x = torch.zeros((ny, nx), dtype=torch.float64, device=dev)
+        for d in range(-R, R + 1):
+            lo, hi = max(0, -d), min(nx, nx - d)
+            if lo < hi:
+                along_x[:, lo:hi] += g[d + R] * ok[:, lo + d:hi + d]
+        norm = torch.zeros((ny, nx), dtype=torch.float64, device=dev)
+        for d in range(-R, R + 1):
+            lo, hi = max(0, -d), min(ny, ny - d)
+            if lo < hi:
+                norm[lo:hi] += g[d + R] * along_x[lo + d:hi + d]
+        inv = torch.zeros(Jp, dtype=torch.float64, device=dev)
+        inv[:J] = torch.where(ok, 1.0 / norm, torch.zeros_like(norm)).reshape(-1)
+        self.inv_norm = inv.to(torch.float32)
+        self.prior = torch.exp(logp).to(torch.float32)          # 0 where the bin is not admissible, and in the padding
+        self._taps32 = [float(np.float32(v)) for v in self.taps[R:]]
+        self._max_windows_per_call = None
+
+    def _populations(self):
+        return self.decoder._populations()
+
+    def _lik_bias(self, window):
+        """-tau S_j, -inf in the bins that are not admissible and in the padding: float32 (Jp,), formed in float64"""
+        dec = self.decoder
+        tau = _check_window(window) * dec.dt
+        b = -tau * dec.S.to(torch.float64)
+        return torch.where(torch.isfinite(dec.log_prior), b, torch.full_like(b, -float("inf"))).to(torch.float32)
+
+    def filter_inputs_tensor(self, inputs, window=1, restart=None, state=None):
+        """The filter over inputs that are not in a history, as `BayesianDecoder.decode_inputs_tensor` takes them: a list of
+        uint8 count or float32 rate tensors `[T][n_l][Bp]`, consecutive windows -> (float32 `[T][6][Bp]`, state).  `restart`:
+        bool or uint8 tensor (T, Bp) or None.  `state`: None starts a new run; the state returned continues one."""
+        dec = self.decoder
+        inputs = list(inputs)
+        if len(inputs) != len(dec.widths) or any(int(x.shape[1]) != w for x, w in zip(inputs, dec.widths)):
+            raise ValueError(f"this decoder takes {len(dec.widths)} input tensors (T, n_l, Bp) of widths {dec.widths}")
+        T, Bp = int(inputs[0].shape[0]), int(inputs[0].shape[2])
+        dev, Jp = inputs[0].device, int(dec.S.shape[0])
+        tau = _check_window(window) * dec.dt
+        out = torch.empty((T, _L.BAYES_OUT_ROWS, Bp), dtype=torch.float32, device=dev)
+        first = state is None
+        if first:
+            state = (torch.empty((Jp, Bp), dtype=torch.float32, device=dev), torch.empty((Jp, Bp), dtype=torch.float32, device=dev),
+                     torch.empty(_ops.bayes_filter_workspace_floats(Jp, Bp), dtype=torch.float32, device=dev))
+        bias = self._lik_bias(window)
+        step = max(1, min(65535, FILTER_LOGLIK_BYTES // (4 * Jp * Bp)))
+        if self._max_windows_per_call is not None:
+            step = max(1, min(step, int(self._max_windows_per_call)))
+        ny, nx = self.grid_shape
+        for o in range(0, T, step):
+            # the likelihood stage: riab_feedforward's store-epilogue GEMM on float32 counts (k = tau x rate for rates)
+            x = [t[o:o + step].to(torch.float32) if t.dtype == torch.uint8 else t[o:o + step] * float(np.float32(tau)) for t in inputs]
+            loglik = torch.ops.riab.feedforward(x, dec.log_rates, bias, _L.ACTIVATIONS["linear"], [0.0, 0.0, 0.0, 0.0])
+            torch.ops.riab.bayes_filter(loglik, dec.n_bins, ny, nx, self._taps32, self.mixing, self.prior, self.inv_norm,
+                                        dec.centres, None if restart is None else restart[o:o + step].contiguous(),
+                                        first and o == 0, state[0], state[1], state[2], out[o:o + step])
+        return out, state
+
+    def decode_all_tensor(self, t_start=None, t_end=None, window=None, inputs="spikes", restart=None):
+        """Every output of the consecutive windows `BayesianDecoder.decode_all_tensor` decodes (the same rows, the same
+        counts), filtered forward from the first: float32 `[T'][6][Bp]`, rows as there except that row 4 is the predictive log
+        likelihood log p(k_t | k_<t).  `restart`: a bool tensor or array (T', B) — or (T', Bp) —; a set flag starts that
+        agent's filter afresh at that window (episode ends, the edges of a ReplayAgent's history["replay"])."""
+        dec = self.decoder
+        agent, hists, _start, window, n_windows, pieces = dec._windows(t_start, t_end, window, inputs)
+        dev, Bp = agent._device, agent._Bp
+        if n_windows == 0:
+            return torch.empty((0, _L.BAYES_OUT_ROWS, Bp), dtype=torch.float32, device=dev)
+        flags = None
+        if restart is not None:
+            r = torch.as_tensor(np.asarray(restart) if not torch.is_tensor(restart) else restart).to(dev)
+            if r.dim() != 2 or int(r.shape[0]) != n_windows or int(r.shape[1]) not in (agent._B, Bp):
+                raise ValueError(f"restart must be ({n_windows}, {agent._B}): one flag per window and agent, got {tuple(r.shape)}")
+            flags = torch.zeros((n_windows, Bp), dtype=torch.uint8, device=dev)
+            flags[:, :int(r.shape[1])] = r != 0
+        if window == 1:      # the rows are the samples: read in place, piece by piece
+            runs = [([h.chunks[c][r:r + length] for h, (c, r) in zip(hists, first)], row0, length) for first, length, row0 in pieces]
+        else:
+            counts = [torch.zeros((n_windows, w, Bp), dtype=torch.uint8, device=dev) for w in dec.widths]
+            for first, length, row0 in pieces:
+                for h, (c, r), cnt in zip(hists, first, counts):
+                    torch.ops.riab.history_window_counts(h.chunks[c][r:r + length], row0, window, cnt)
+            runs = [(counts, 0, n_windows)]
+        parts, state = [], None
+        for x, w0, n in runs:
+            out, state = self.filter_inputs_tensor(x, window, None if flags is None else flags[w0:w0 + n], state)
+            parts.append(out)
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+    def decode_tensor(self, t_start=None, t_end=None, window=None, inputs="spikes", estimate="mean", restart=None):
+        """The filtered position of every window: float32 `[T'][2][Bp]`, the posterior mean (estimate="mean") or the MAP
+        bin's centre ("map")."""
+        if estimate not in ("mean", "map"):
+            raise ValueError(f"estimate must be 'mean' or 'map', got {estimate!r}")
+        lo = OUT_ROWS[estimate][0]
+        return self.decode_all_tensor(t_start, t_end, window, inputs, restart)[:, lo:lo + 2]
+
+    def _target_tensor(self, t_start, t_end):
+        return self.decoder._target_tensor(t_start, t_end)
+
+
 def _check_window(window):
     if isinstance(window, bool) or int(window) != window or not 1 <= int(window) <= MAX_WINDOW:
         raise ValueError(f"window must be an integer in 1..{MAX_WINDOW} rows, got {window}")
@@ -234,7 +402,7 @@ def fit_bayesian_decoder(populations, tuning="history", bin_size=0.05, t_start=N
         curves = [p.get_state_tensor(evaluate_at="all")[:, :J].to(torch.float64) for p in populations]
         centres = torch.from_numpy(np.ascontiguousarray(np.asarray(env.flattened_discrete_coords, dtype=np.float64).T))
         return BayesianDecoder.from_tuning(curves, centres, dt, rate_floor=rate_floor, window=window, populations=populations,
-                                           grid_shape=shape, tuning=tuning, prior=prior)
+                                           grid_shape=shape, tuning=tuning, prior=prior, bin_width=float(env.dx))
     centres, ny, nx = grid_centres(agent.Environment.extent, bin_size)
     if ny * nx > MAX_BINS:
         raise ValueError(f"bins of {bin_size} make a grid of {ny * nx} bins, a Bayesian decoder takes 1..{MAX_BINS}: use larger bins")
@@ -247,4 +415,4 @@ def fit_bayesian_decoder(populations, tuning="history", bin_size=0.05, t_start=N
     return BayesianDecoder.from_tuning(curves, torch.from_numpy(centres), dt, admissible=~zero.reshape(-1),
                                        prior_weights=visits.reshape(-1) if prior == "occupancy" else None,
                                        rate_floor=rate_floor, window=window, populations=populations, grid_shape=(ny, nx),
-                                       tuning=tuning, prior=prior)
+                                       tuning=tuning, prior=prior, bin_width=float(bin_size))

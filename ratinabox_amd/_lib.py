@@ -162,6 +162,7 @@ RATEMAP_MAX_BINS, RATEMAP_DROPPED, RATEMAP_FP32_RUN = 4096, 0xFFFF, 0     # riab
 MOMENTS_MAX_TARGETS, MOMENTS_MAX_M = 4, 4096                            # riab_hip.h RIAB_MOMENTS_MAX_*
 GP_MAX_TRAIN, GP_MAX_OUT = 16384, 4                                     # riab_hip.h RIAB_GP_MAX_*
 BAYES_MAX_WINDOW, BAYES_OUT_ROWS = 255, 6                               # riab_hip.h RIAB_BAYES_*
+BAYES_FILTER_MAX_RADIUS = 16                                            # riab_hip.h RIAB_BAYES_FILTER_MAX_RADIUS
 CU_PROBE_WORDS = 4097                                                  # riab_hip.h RIAB_CU_PROBE_WORDS
 STEP1_MAIL_STRIDE = 1088                                                # riab_hip.h RIAB_STEP1_MAIL_STRIDE
 
@@ -274,6 +275,9 @@ PROTOTYPES = {
                                              C.c_void_p, C.c_void_p]),
     "riab_bayes_decode": (C.c_int, [C.POINTER(RiabFFInput), C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
+    "riab_bayes_filter": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                                    C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "riab_fill": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "riab_plan_create": (C.c_void_p, [C.POINTER(RiabEnv), C.POINTER(RiabMotion), C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),

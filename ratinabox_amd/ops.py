@@ -20,6 +20,7 @@ Functional operators (return a new tensor)
     bayes_decode  Poisson maximum-likelihood position decoding of spike counts (or rates) over bins       float32 (T, 6, B)
 In-place operators
     history_window_counts  spike rows of a history piece added into the uint8 counts of their time windows
+    bayes_filter     the Bayesian decoder with a continuity prior: a forward filter over consecutive windows, state carried
     history_moments  the float64 moment matrix of [rates ; targets ; 1] over history rows: what a ridge decoder is solved from
     td_forward_tail  the tail of ValueNeuron.update(): dV/dt, V_last and (optionally) the eligibility traces
     td_update        ValueNeuron.update_weights(reward): TD error, batch-mean gradient on the matrix cores, W^T updated
@@ -741,3 +742,52 @@ def bayes_decode(inputs: List[Tensor], log_rates: List[Tensor], bias: Tensor, ce
                                       _L.ptr(centres), int(n_bins), Jp, T, B, _L.ptr(out), int(block_tiles),
                                       _L.current_stream()), "riab_bayes_decode")
     return out
+
+
+def bayes_filter_splits(Jp: int) -> int:
+    """RIAB_BAYES_FILTER_SPLITS(Jp): how many ranges the bins are split into (a function of Jp alone)"""
+    return Jp // 32 if Jp <= 512 else (Jp + 127) // 128
+
+
+def bayes_filter_workspace_floats(Jp: int, B: int) -> int:
+    """RIAB_BAYES_FILTER_WORKSPACE_FLOATS(Jp, B): the partial softmax states [S][5][B] and one 32-bit flag per column"""
+    return (5 * bayes_filter_splits(Jp) + 1) * B
+
+
+@_register("bayes_filter(Tensor loglik, int n_bins, int ny, int nx, float[] taps, float mixing, Tensor prior, Tensor inv_norm, "
+           "Tensor centres, Tensor? restart, bool first, Tensor(a!) post, Tensor(b!) tmp, Tensor(c!) workspace, "
+           "Tensor(d!) out) -> ()",
+           lambda loglik, n_bins, ny, nx, taps, mixing, prior, inv_norm, centres, restart, first, post, tmp, workspace, out: None)
+def bayes_filter(loglik: Tensor, n_bins: int, ny: int, nx: int, taps: List[float], mixing: float, prior: Tensor,
+                 inv_norm: Tensor, centres: Tensor, restart: Optional[Tensor], first: bool, post: Tensor, tmp: Tensor,
+                 workspace: Tensor, out: Tensor) -> None:
+    """The Bayesian decoder's forward filter over W consecutive windows (riab_bayes_filter, two launches per window, all
+    issued by one native call): l_t = loglik[t] + log pred_t with pred_t the last posterior carried through a Gaussian step of
+    taps g[0..R] (restricted to admissible bins, normalised per source bin by `inv_norm`) mixed with the prior, pred = prior
+    on a fresh column.  loglik float32 (W, Jp, B); taps R + 1 floats; prior, inv_norm float32 (Jp,); centres float32 (2, Jp);
+    restart uint8 / bool (W, B) or None; first: a new run, else the state in post / tmp / workspace is continued; post, tmp
+    float32 (Jp, B); workspace float32 of `bayes_filter_workspace_floats(Jp, B)` elements; out float32 (W, 6, B), written."""
+    if loglik.dtype != torch.float32 or loglik.dim() != 3 or not loglik.is_contiguous():
+        raise ValueError("loglik must be a contiguous float32 tensor (W, Jp, B)")
+    W, Jp, B = (int(x) for x in loglik.shape)
+    dev = loglik.device
+    for name, t, shape in (("prior", prior, (Jp,)), ("inv_norm", inv_norm, (Jp,)), ("centres", centres, (2, Jp)),
+                           ("post", post, (Jp, B)), ("tmp", tmp, (Jp, B)), ("out", out, (W, _L.BAYES_OUT_ROWS, B))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous float32 tensor {shape} on loglik's device")
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != dev or \
+            workspace.numel() < bayes_filter_workspace_floats(Jp, B):
+        raise ValueError(f"workspace must be a contiguous float32 tensor of {bayes_filter_workspace_floats(Jp, B)} elements")
+    if restart is not None:
+        if restart.dtype == torch.bool:
+            restart = restart.view(torch.uint8)
+        if restart.dtype != torch.uint8 or tuple(restart.shape) != (W, B) or not restart.is_contiguous() or restart.device != dev:
+            raise ValueError(f"restart must be a contiguous uint8 or bool tensor ({W}, {B}) on loglik's device")
+    radius = len(taps) - 1
+    if not 1 <= radius <= _L.BAYES_FILTER_MAX_RADIUS:
+        raise ValueError(f"taps must hold g[0..R] for a radius R in 1..{_L.BAYES_FILTER_MAX_RADIUS}, got {len(taps)} values")
+    g = (C.c_float * (radius + 1))(*[float(x) for x in taps])
+    _L.check(_L.lib.riab_bayes_filter(_L.ptr(loglik), W, int(n_bins), Jp, int(ny), int(nx), B, radius, g, float(mixing),
+                                      _L.ptr(prior), _L.ptr(inv_norm), _L.ptr(centres),
+                                      None if restart is None else _L.ptr(restart), 1 if first else 0, _L.ptr(post),
+                                      _L.ptr(tmp), _L.ptr(workspace), _L.ptr(out), _L.current_stream()), "riab_bayes_filter")
