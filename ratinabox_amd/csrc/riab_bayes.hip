@@ -8,14 +8,15 @@
 //
 // and a (window, agent) sample is reduced to six numbers: the posterior mean sum_j softmax(l)_j x_j, the centre of the
 // lowest-indexed bin among the maxima (MAP), logsumexp_j l_j and softmax(l) at the MAP bin.  The sum over cells is a GEMM
-// [J bins] x [n cells] x [samples], which is gp_kernel's main loop (csrc/riab_gp.hip): bins take the place of the training
-// samples, a running softmax the place of the RBF sum.  The [samples] x [J] matrix lives in accumulator registers only.
+// [J bins] x [n cells] x [samples], which runs on the streamed core of csrc/riab_mfma_slab.h (layouts, bounds and barriers are
+// stated there), as gp_kernel's does: the table of log rates is operand A, a running softmax takes the place of the RBF sum.
+// The [samples] x [J] matrix lives in accumulator registers only.
 //
-//   bayes_kernel<MT, COUNTS>   grid (position tiles of 128 x windows), 4 waves; wave w owns positions [32w, 32w + 32).  The
-//                   bins are walked in blocks of 32 MT; for each block the whole K (every population, slabs of 16 through
-//                   double-buffered LDS) is contracted on v_mfma_f32_32x32x2_f32 into MT accumulator tiles.  The inputs
-//                   are uint8 counts (COUNTS: widened to fp32 on the way into LDS; small integers are exact) or fp32 rates
-//                   multiplied by `scale`.  The epilogue adds bias_j and folds the block into the lane's running state.
+//   bayes_kernel<MT, COUNTS>   grid (position tiles of 128 x windows), 4 waves.  The bins are walked in blocks of 32 MT; for
+//                   each block the whole K (every population) is contracted into MT accumulator tiles.  The inputs are uint8
+//                   counts (COUNTS: widened to fp32 by the fetch; small integers are exact) or fp32 rates multiplied by
+//                   `scale` (by the fetch too).  The stash's select zeroes the table's padding bins J..Jp-1 whatever they
+//                   hold.  The epilogue adds bias_j and folds the block into the lane's running state.
 //
 // Arithmetic of one position, in order.  dot_j = the k-ordered fmaf chain of the MFMA; l_j = dot_j + bias_j.  Each half-wave
 // (rows 4h..4h+3 of every group of 8 bins) keeps (m, Z, sx, sy, arg) and takes its bins four at a time, j ascending: the
@@ -36,16 +37,12 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "riab_hip.h"
+#include "riab_device.h"   // LOG2E
+#include "riab_mfma_slab.h"
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-constexpr int BY_KT = 16;    // K slab
-constexpr int BY_NB = 128;   // positions per block
-constexpr float BY_LOG2E = 1.44269504088896341f;
+using namespace riab;
 
 struct BayesArgs {
   const void* rows[RIAB_FF_MAX_INPUTS];    // [T][n_in][B]: uint8 counts or fp32 rates
@@ -61,26 +58,10 @@ struct BayesArgs {
   float* out;             // [T][6][B]
 };
 
-// One thread's share of a K slab, as in gp_kernel: waves 0-1 fetch the table, waves 2-3 the inputs; a thread takes rows
-// kbase + 2s (s = 0..3) x 4 consecutive columns.  Rows past K read row K - 1 and columns outside the problem column 0
-// (both zeroed by the stash), so the fetch is branch-free and in bounds.
-struct BayesSlab {
-  v4f v[4];
-};
-
-__device__ __forceinline__ BayesSlab by_fetch_f32(const float* src, int64_t ld, int col, int K, int kbase) {
-  BayesSlab f;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int k = kbase + 2 * s;
-    const int kc = k < K ? k : K - 1;
-    f.v[s] = *reinterpret_cast<const v4f*>(src + (int64_t)kc * ld + col);
-  }
-  return f;
-}
-
-__device__ __forceinline__ BayesSlab by_fetch_u8(const uint8_t* src, int64_t ld, int col, int K, int kbase) {
-  BayesSlab f;
+// bayes_kernel's fetch of uint8 counts, widened to fp32 (small integers are exact): fetch_f32's rows and clamps, 4 bytes
+// where that reads 16.
+__device__ __forceinline__ Slab by_fetch_u8(const uint8_t* src, int64_t ld, int col, int K, int kbase) {
+  Slab f;
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     const int k = kbase + 2 * s;
@@ -100,64 +81,38 @@ struct BayesState {
 // 3 waves per SIMD keep 3 workgroups on a CU, as gp_kernel has them.  The 128-bin form wants 172-174 registers where 168
 // are to be had: held to (3, 3) its rates form put two of them in scratch; asked for 2..3 waves the compiler finds 168
 // without scratch (no kernel of the library but the known ones may have a stack frame: tests/test_handover_isa.py).
+// On the shared core the rates form comes out at 165 either way; the range stays, since 3 registers of slack is what a
+// change of statement order moves.
 template <int MT, bool COUNTS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MT == 4 && !COUNTS) ? 2 : 3, 3)))
 void bayes_kernel(const BayesArgs a) {
-  // LDS slab layout [g][kh][column][s] (k = 8g + 2s + kh), columns XOR-swizzled, double-buffered: ff_kernel's
-  __shared__ __align__(16) float s_a[2][BY_KT / 4][MT * 32][4];   // table slab
-  __shared__ __align__(16) float s_b[2][BY_KT / 4][BY_NB][4];     // input slab
+  __shared__ __align__(16) SlabTiles<MT> lds;                     // table slab (A) and input slab
   __shared__ __align__(16) float s_bias[MT * 32];                 // bias of the bin block (bins >= J: -inf)
   __shared__ __align__(16) float s_cx[MT * 32];                   // centres of the bin block
   __shared__ __align__(16) float s_cy[MT * 32];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int t = blockIdx.x / a.tiles;
-  const int64_t b0 = (int64_t)(blockIdx.x - t * a.tiles) * BY_NB;
+  const int64_t b0 = (int64_t)(blockIdx.x - t * a.tiles) * NB;
 
-  const bool is_b = wave >= 2;                           // wave-uniform
-  const int c4 = (tid & 31) * 4, rg = (tid >> 5) & 3;    // rg = 2g + kh
-  const int krow = (rg >> 1) * 8 + (rg & 1);
+  const SlabRole<MT> role(lds, tid, wave);
+  const Frag<MT> fr(lane, wave);
+  const bool is_b = role.is_b;
+  const int c4 = role.c4;
   const bool b_ok = b0 + c4 < a.B;                       // (B % 4 == 0: a quad is wholly inside or outside)
-  const int sw = (c4 >> 3) & 7;
-  float* const s_dst = is_b ? &s_b[0][rg][0][0] : &s_a[0][rg][0][0];
-  const int buf_stride = is_b ? (BY_KT / 4) * BY_NB * 4 : (BY_KT / 4) * MT * 32 * 4;
-  const int kh = lane >> 5, j = lane & 31;
-  const int jb = (wave * 32 + j) ^ (((wave * 32 + j) >> 3) & 7);
-  int ja[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) ja[mt] = (mt * 32 + j) ^ (((mt * 32 + j) >> 3) & 7);
+  const int kh = fr.kh, j = fr.j;
   const float neg_inf = -INFINITY;
 
   BayesState st = {neg_inf, 0.0f, 0.0f, 0.0f, 0};
   int buf = 0;
   for (int m0 = 0; m0 < a.Jp; m0 += MT * 32) {   // bin blocks
-    const bool col_ok = is_b ? b_ok : (c4 < MT * 32 && m0 + c4 < a.Jp);
+    // the table's padding bins J..Jp-1 are zeroed whatever they hold: their products must not reach the softmax as NaN
+    const SlabMask mask = {is_b ? b_ok : role.a_quad_ok(m0, a.Jp), is_b ? 4 : a.J - (m0 + c4)};
     // the block's and the tile's offsets are wave-uniform and go into the base pointer: the lane keeps one 32-bit column
-    const int col = col_ok ? c4 : 0;
-    auto fetch = [&](int l, int K, int kbase) {
-      if (!is_b) return by_fetch_f32(a.wt[l] + m0, a.Jp, col, K, kbase);
-      if (COUNTS) return by_fetch_u8(static_cast<const uint8_t*>(a.rows[l]) + (int64_t)t * K * a.B + b0, a.B, col, K, kbase);
-      return by_fetch_f32(static_cast<const float*>(a.rows[l]) + (int64_t)t * K * a.B + b0, a.B, col, K, kbase);
-    };
-    // 4x4 register transpose [s][column] -> [column][s]; rows >= K and columns outside the problem become 0 (the table's
-    // padding bins J..Jp-1 too, whatever they hold: their products must not reach the softmax as NaN)
-    auto stash = [&](const BayesSlab& f, int to, int K, int k0) {
-      if (!is_b && c4 >= MT * 32) return;
-      const float mul = (is_b && !COUNTS) ? a.scale : 1.0f;
-      const int jlim = is_b ? 4 : a.J - (m0 + c4);   // table columns of the quad that are bins of the problem
-      v4f v[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) v[s] = (col_ok && k0 + krow + 2 * s < K) ? f.v[s] * mul : v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        *reinterpret_cast<v4f*>(s_dst + to * buf_stride + ((c4 + i) ^ sw) * 4) =
-            i < jlim ? v4f{v[0][i], v[1][i], v[2][i], v[3][i]} : v4f{0.f, 0.f, 0.f, 0.f};
-    };
+    const int col = mask.col_ok ? c4 : 0;
     v16f acc[MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
+    for (int i = 0; i < MT; ++i) zero_acc(acc[i]);
     for (int l = 0; l < a.n_layers; ++l) {
       const int K = a.n_in[l];
       __syncthreads();  // the slab and the epilogue tables before this have been consumed
@@ -167,31 +122,16 @@ void bayes_kernel(const BayesArgs a) {
         s_cx[tid] = in ? a.centres[m0 + tid] : 0.0f;
         s_cy[tid] = in ? a.centres[(int64_t)a.Jp + m0 + tid] : 0.0f;
       }
-      stash(fetch(l, K, krow), buf, K, 0);
-      __syncthreads();
-      for (int k0 = 0; k0 < K; k0 += BY_KT) {
-        const bool more = k0 + BY_KT < K;  // block-uniform
-        BayesSlab nxt;
-        if (more) nxt = fetch(l, K, k0 + BY_KT + krow);
+      contract_population(lds, role, fr, buf, K, mask, acc, [&](int kbase) {
+        if (!is_b) return fetch_f32(a.wt[l] + m0, a.Jp, col, K, kbase);
+        if (COUNTS) return by_fetch_u8(static_cast<const uint8_t*>(a.rows[l]) + (int64_t)t * K * a.B + b0, a.B, col, K, kbase);
+        Slab f = fetch_f32(static_cast<const float*>(a.rows[l]) + (int64_t)t * K * a.B + b0, a.B, col, K, kbase);
 #pragma unroll
-        for (int g = 0; g < BY_KT / 8; ++g) {
-          const v4f bq = *reinterpret_cast<const v4f*>(&s_b[buf][2 * g + kh][jb][0]);
-          v4f aq[MT];
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) aq[mt] = *reinterpret_cast<const v4f*>(&s_a[buf][2 * g + kh][ja[mt]][0]);
-#pragma unroll
-          for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[mt][s], bq[s], acc[mt], 0, 0, 0);
-        }
-        if (more) {
-          stash(nxt, buf ^ 1, K, k0 + BY_KT);  // the other buffer was last read one iteration ago (barrier below)
-          __syncthreads();
-          buf ^= 1;
-        }
-      }
+        for (int s = 0; s < 4; ++s) f.v[s] *= a.scale;   // (what the stash zeroes it zeroes whatever the product is)
+        return f;
+      });
     }
-    // ---- epilogue of the block: C/D layout col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    // ---- epilogue of the block, in the C/D layout of riab_mfma_slab.h: rows 8q + 4kh .. + 3 of tile mt are registers 4q .. 4q + 3
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
@@ -215,7 +155,7 @@ void bayes_kernel(const BayesArgs a) {
           }
         }
         if (mn > st.m) {     // (st.m = -inf: exp2(-inf) = 0 times the zeros an empty state holds)
-          const float sc = __builtin_amdgcn_exp2f((st.m - mn) * BY_LOG2E);
+          const float sc = __builtin_amdgcn_exp2f((st.m - mn) * LOG2E);
           st.Z *= sc;
           st.sx *= sc;
           st.sy *= sc;
@@ -225,7 +165,7 @@ void bayes_kernel(const BayesArgs a) {
         const float ms = st.m == neg_inf ? 0.0f : st.m;   // an empty state subtracts 0: -inf - -inf is never formed
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float p = __builtin_amdgcn_exp2f((v[i] - ms) * BY_LOG2E);
+          const float p = __builtin_amdgcn_exp2f((v[i] - ms) * LOG2E);
           st.Z += p;
           st.sx = __builtin_fmaf(p, cx4[i], st.sx);
           st.sy = __builtin_fmaf(p, cy4[i], st.sy);
@@ -242,7 +182,7 @@ void bayes_kernel(const BayesArgs a) {
   int A = take_o ? arg_o : st.arg;
   A = A < a.J ? A : a.J - 1;
   const float Ms = M == neg_inf ? 0.0f : M;
-  const float wa = __builtin_amdgcn_exp2f((st.m - Ms) * BY_LOG2E), wb = __builtin_amdgcn_exp2f((m_o - Ms) * BY_LOG2E);
+  const float wa = __builtin_amdgcn_exp2f((st.m - Ms) * LOG2E), wb = __builtin_amdgcn_exp2f((m_o - Ms) * LOG2E);
   const float Z = __builtin_fmaf(Z_o, wb, st.Z * wa);
   const float sx = __builtin_fmaf(sx_o, wb, st.sx * wa);
   const float sy = __builtin_fmaf(sy_o, wb, st.sy * wa);
@@ -332,7 +272,7 @@ extern "C" int riab_bayes_decode(const RiabFFInput* inputs, int32_t n_inputs, in
   for (int l = 0; l < n_inputs; ++l)
     if (((uintptr_t)inputs[l].wt & 15) || ((uintptr_t)inputs[l].rates & (inputs_are_counts ? 3 : 15))) return RIAB_EALIGN;
   if (((uintptr_t)bias | (uintptr_t)centres | (uintptr_t)out) & 15) return RIAB_EALIGN;
-  const int64_t tiles = (B + BY_NB - 1) / BY_NB;
+  const int64_t tiles = (B + NB - 1) / NB;
   if (tiles > 0x7fffffffLL || T > 0x7fffffffLL / tiles) return RIAB_ETOOBIG;   // (a division: T * tiles could wrap)
   if (T == 0) return RIAB_OK;
   a.n_layers = n_inputs;

@@ -33,14 +33,15 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "riab_hip.h"
+#include "riab_device.h"   // LOG2E
 
 namespace {
+
+using riab::LOG2E;
 
 constexpr int BF_MAXR = RIAB_BAYES_FILTER_MAX_RADIUS;
 constexpr int BF_SEG = 64;    // bins staged in LDS at a time (plus the halo)
 constexpr int BF_COLS = 64;   // columns per workgroup: one per lane
-constexpr float BF_LOG2E = 1.44269504088896341f;
 
 struct FilterArgs {
   const float* loglik;      // [Jp][B] of this window
@@ -77,7 +78,7 @@ __device__ __forceinline__ void bf_merge(float& M, float& Z, float& sx, float& s
   const float Mn = take_o ? m_o : M;
   A = take_o ? arg_o : A;
   const float Ms = Mn == -INFINITY ? 0.0f : Mn;   // an empty state subtracts 0
-  const float wa = __builtin_amdgcn_exp2f((M - Ms) * BF_LOG2E), wb = __builtin_amdgcn_exp2f((m_o - Ms) * BF_LOG2E);
+  const float wa = __builtin_amdgcn_exp2f((M - Ms) * LOG2E), wb = __builtin_amdgcn_exp2f((m_o - Ms) * LOG2E);
   Z = __builtin_fmaf(Z_o, wb, Z * wa);
   sx = __builtin_fmaf(sx_o, wb, sx * wa);
   sy = __builtin_fmaf(sy_o, wb, sy * wa);
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(256) void filter_post_kernel(const FilterArgs a) {
     const float v = a.loglik[(int64_t)j * a.B + bb] + lp;
     if (live) *dst = v;
     if (v > m) {   // strictly greater, j ascending: the lowest index wins a tie; NaN never wins
-      const float sc = __builtin_amdgcn_exp2f((m - v) * BF_LOG2E);
+      const float sc = __builtin_amdgcn_exp2f((m - v) * LOG2E);
       Z *= sc;
       sx *= sc;
       sy *= sc;
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(256) void filter_post_kernel(const FilterArgs a) {
       arg = j;
     }
     const float ms = m == neg_inf ? 0.0f : m;   // an empty state subtracts 0: -inf - -inf is never formed
-    const float p = __builtin_amdgcn_exp2f((v - ms) * BF_LOG2E);
+    const float p = __builtin_amdgcn_exp2f((v - ms) * LOG2E);
     Z += p;
     sx = __builtin_fmaf(p, a.centres[j], sx);
     sy = __builtin_fmaf(p, a.centres[(int64_t)a.Jp + j], sy);
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(256) void filter_blur_kernel(const FilterArgs a) {
         const int i = i0 + u, j = t0 - a.R + i;
         if (i < n + 2 * a.R) {
           const bool in = j >= 0 && j < a.J;
-          const float q = __builtin_amdgcn_exp2f((l[u] - M) * BF_LOG2E) * (a.inv_norm[in ? j : 0] * rZ);
+          const float q = __builtin_amdgcn_exp2f((l[u] - M) * LOG2E) * (a.inv_norm[in ? j : 0] * rZ);
           s_q[i][lane] = in ? q : 0.0f;
         }
       }

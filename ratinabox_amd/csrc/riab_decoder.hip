@@ -28,9 +28,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "riab_hip.h"
+#include "riab_device.h"   // finite_bits
 
 namespace {
+
+using riab::finite_bits;
 
 constexpr int kBlock = 256;
 constexpr int kRows = 64;        // rows of z per block (4 tiles of 16)
@@ -73,8 +75,6 @@ __device__ __forceinline__ RowSource row_source(const MomentArgs& a, const float
   }
   return s;
 }
-
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 __device__ __forceinline__ f32x4 select4(const bool* keep, f32x4 v) {
   f32x4 r;

@@ -106,6 +106,12 @@ __device__ __forceinline__ void store_stream(uint32_t* p, uint32_t v) {
 typedef const __attribute__((address_space(4))) float* const_f32_ptr;
 __device__ __forceinline__ const_f32_ptr as_const_table(const float* p) { return (const_f32_ptr)(const void*)p; }
 
+// log2 e, for exp(x) as v_exp_f32(x * LOG2E)
+constexpr float LOG2E = 1.44269504088896341f;
+
+// neither an infinity nor a NaN, by the exponent bits (a comparison would be folded away under fast-math assumptions)
+__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
 // fp32 uniform in [0,1) with 24 random bits — exactly representable, so the
 // host can regenerate it bit for bit.
 __device__ __forceinline__ float u01_24(uint32_t w) { return (float)(w >> 8) * 0x1.0p-24f; }

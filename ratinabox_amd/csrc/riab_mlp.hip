@@ -3,11 +3,11 @@
 //     h_0 = concat_l I_l          h_i = act_i(W_i h_{i-1} + bias_i)          out = h_L
 //
 // N = positions (agents x time rows), as in riab_ff.hip; a wave owns 32 positions and ALL rows of every layer.  On the fp32
-// matrix cores (v_mfma_f32_32x32x2_f32: exact fp32), lane l = 32 kh + j:
-//     A[i = l&31][k = l>>5],  B[k = l>>5][j = l&31],  C/D: column j, row (reg&3) + 8*(reg>>2) + 4*kh.
+// matrix cores (v_mfma_f32_32x32x2_f32: exact fp32), lane l = 32 kh + j, in the fragment layout of riab_mfma_slab.h.
 //
-// Layer 0 streams from memory like ff_kernel: K slabs of 16, double-buffered in LDS, XOR-swizzled columns, clamped
-// fetches.  The weights are torch.nn.Linear.weight read in place ([n_out][n_in], k contiguous), so a thread's 16-byte
+// Layer 0 streams from memory as that header describes (K slabs of 16, double-buffered in LDS, swizzled columns, clamped
+// fetches zeroed in the stash, two barriers per slab pair), with its types and swizzle() but a loop of its own: the A tile
+// is a fixed 128 rows, the rates tile 32 nw positions, and the weights are torch.nn.Linear.weight read in place ([n_out][n_in], k contiguous), so a thread's 16-byte
 // fetch of W is four consecutive k of one row; a slab maps k = 4 rg + s to (LDS row group rg, element s) for both operands
 // and the W stash needs no transpose (the rates stash keeps ff_kernel's 4x4 register transpose).
 //
@@ -24,15 +24,12 @@
 
 #include "riab_act.h"
 #include "riab_device.h"
+#include "riab_mfma_slab.h"   // v4f, v16f, KT, swizzle()
 
 namespace riab {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-constexpr int MLP_KT = 16;        // K slab of layer 0
 constexpr int MLP_MAX_INPUTS = 8;
-constexpr int MLP_A_FLOATS = 2 * (MLP_KT / 4) * 128 * 4;  // LDS: W slab [buf][rg][row][s], 16 KB; behind it the rates slab
+constexpr int MLP_A_FLOATS = 2 * (KT / 4) * 128 * 4;  // LDS: W slab [buf][rg][row][s], 16 KB; behind it the rates slab
 
 struct MLPLayerArgs {
   const float* w;     // [n_out][n_in]
@@ -87,19 +84,19 @@ template <int MT, int MAXT>
 __device__ __forceinline__ void mlp_first_layer(const MLPArgs& a, float* smem, int m0, int t, int64_t b0, int nw,
                                                 v16f (&acc)[MAXT]) {
   static_assert(MT <= MAXT, "tile count");
-  const int tid = threadIdx.x, lane = tid & 63, nt = nw * 64, NB = nw * 32;
+  const int tid = threadIdx.x, lane = tid & 63, nt = nw * 64, nb = nw * 32;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   float* const s_a = smem;                 // [2][4][128][4]
-  float* const s_b = smem + MLP_A_FLOATS;  // [2][4][NB][4]
+  float* const s_b = smem + MLP_A_FLOATS;  // [2][4][nb][4]
   const MLPLayerArgs& L = a.layer[0];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
 
-  // rates role (threads < NB): row group rg_b, 4 consecutive positions; rows k0 + 4 rg_b + s, s = 0..3
-  const bool has_b = tid < NB;
-  const int cg = NB / 4, c4 = (tid % cg) * 4, rg_b = has_b ? tid / cg : 0;
+  // rates role (threads < nb): row group rg_b, 4 consecutive positions; rows k0 + 4 rg_b + s, s = 0..3
+  const bool has_b = tid < nb;
+  const int cg = nb / 4, c4 = (tid % cg) * 4, rg_b = has_b ? tid / cg : 0;
   const bool col_ok = has_b && b0 + c4 < a.B;
   const int64_t col = col_ok ? b0 + c4 : 0;  // (B % 4 == 0: a float4 of positions is wholly inside or outside)
   const int sw = (c4 >> 3) & 7;
@@ -109,10 +106,10 @@ __device__ __forceinline__ void mlp_first_layer(const MLPArgs& a, float* smem, i
   constexpr int A_MAX = A_ITEMS / 64;  // items of a thread when the block is one wave
 
   const int kh = lane >> 5, j = lane & 31;
-  const int jb = (wave * 32 + j) ^ (((wave * 32 + j) >> 3) & 7);
+  const int jb = swizzle(wave * 32 + j);
   int ja[MT];
 #pragma unroll
-  for (int mt = 0; mt < MT; ++mt) ja[mt] = (mt * 32 + j) ^ (((mt * 32 + j) >> 3) & 7);
+  for (int mt = 0; mt < MT; ++mt) ja[mt] = swizzle(mt * 32 + j);
 
   int buf = 0;
   for (int l = 0; l < a.n_inputs; ++l) {
@@ -145,7 +142,7 @@ __device__ __forceinline__ void mlp_first_layer(const MLPArgs& a, float* smem, i
         v4f v[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) v[s] = (col_ok && k0 + 4 * rg_b + s < K) ? fb[s] : v4f{0.f, 0.f, 0.f, 0.f};
-        float* dst = s_b + ((b * 4 + rg_b) * NB) * 4;
+        float* dst = s_b + ((b * 4 + rg_b) * nb) * 4;
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<v4f*>(dst + ((c4 + i) ^ sw) * 4) = v4f{v[0][i], v[1][i], v[2][i], v[3][i]};
       }
@@ -154,7 +151,7 @@ __device__ __forceinline__ void mlp_first_layer(const MLPArgs& a, float* smem, i
         const int idx = tid + i * nt;
         if (idx < A_ITEMS) {
           const int am = idx >> 2;
-          *reinterpret_cast<v4f*>(s_a + ((b * 4 + (idx & 3)) * 128 + (am ^ ((am >> 3) & 7))) * 4) = fa[i];
+          *reinterpret_cast<v4f*>(s_a + ((b * 4 + (idx & 3)) * 128 + swizzle(am)) * 4) = fa[i];
         }
       }
     };
@@ -162,12 +159,12 @@ __device__ __forceinline__ void mlp_first_layer(const MLPArgs& a, float* smem, i
     fetch(0);
     stash(buf, 0);
     __syncthreads();
-    for (int k0 = 0; k0 < K; k0 += MLP_KT) {
-      const bool more = k0 + MLP_KT < K;  // block-uniform
-      if (more) fetch(k0 + MLP_KT);
+    for (int k0 = 0; k0 < K; k0 += KT) {
+      const bool more = k0 + KT < K;  // block-uniform
+      if (more) fetch(k0 + KT);
 #pragma unroll
-      for (int g = 0; g < MLP_KT / 8; ++g) {
-        const v4f bq = *reinterpret_cast<const v4f*>(s_b + ((buf * 4 + 2 * g + kh) * NB + jb) * 4);
+      for (int g = 0; g < KT / 8; ++g) {
+        const v4f bq = *reinterpret_cast<const v4f*>(s_b + ((buf * 4 + 2 * g + kh) * nb + jb) * 4);
         v4f aq[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) aq[mt] = *reinterpret_cast<const v4f*>(s_a + ((buf * 4 + 2 * g + kh) * 128 + ja[mt]) * 4);
@@ -177,7 +174,7 @@ __device__ __forceinline__ void mlp_first_layer(const MLPArgs& a, float* smem, i
           for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[mt][s], bq[s], acc[mt], 0, 0, 0);
       }
       if (more) {
-        stash(buf ^ 1, k0 + MLP_KT);  // the other buffer was last read one iteration ago (barrier below)
+        stash(buf ^ 1, k0 + KT);  // the other buffer was last read one iteration ago (barrier below)
         __syncthreads();
         buf ^= 1;
       }
@@ -404,7 +401,7 @@ extern "C" int riab_mlp_forward(const float* const* inputs, const int32_t* input
   const int64_t wide = (B + 127) / 128 * T;
   const int nw = wide >= mlp_compute_units() ? 4 : 1;
   const dim3 grid((unsigned)((B + nw * 32 - 1) / (nw * 32)), 1, (unsigned)T);
-  const size_t smem = (size_t)(MLP_A_FLOATS + 2 * (MLP_KT / 4) * (nw * 32) * 4) * sizeof(float);
+  const size_t smem = (size_t)(MLP_A_FLOATS + 2 * (KT / 4) * (nw * 32) * 4) * sizeof(float);
   // the widest activation carried in registers: every hidden width, or the only layer's rows of one pass
   int widest = n_layers == 1 ? (layers[0].n_out < 128 ? layers[0].n_out : 128) : 0;
   for (int i = 0; i + 1 < n_layers; ++i) widest = layers[i].n_out > widest ? layers[i].n_out : widest;
