@@ -521,6 +521,69 @@ def test_form_selection_follows_the_measured_step_and_store_rates(riab):
             assert torch.equal(x, y), label
 
 
+class _Both:
+    """two populations behind the interface _run reads: their rate rows side by side"""
+    def __init__(self, *pops):
+        self.pops = pops
+
+    def update(self):
+        for p in self.pops:
+            p.update()
+
+    def get_history_tensors(self):
+        frs, sps = zip(*(p.get_history_tensors() for p in self.pops))
+        return torch.cat(frs, dim=1), torch.cat(sps, dim=1)
+
+
+def test_real_calls_take_the_decisions_of_the_logic_header(riab):
+    """Form, mode and launch count of real calls equal what csrc/riab_simulate_logic.h decides for their facts on the host
+    alone (tests/test_simulate_logic_cpu.py: the table is shared) — at both sides of the strict mode's 256 steps and of the
+    2048 rows of one kernel, and for two populations under configured step times and store rates — with rows bit-identical
+    to the Python-driven pipeline.  One whole agent group, one cell group."""
+    from tests.test_simulate_logic_cpu import REAL_CALLS_ONE, REAL_CALLS_TWO
+    L = riab._lib
+    names = {1: "one-kernel", 2: "chunks", 4: "populations", 5: "head+pieces"}
+
+    def two(riab, ag):
+        return _Both(riab.PlaceCells(ag, {"n": 8, "save_spikes": False, "wall_geometry": "euclidean"}),
+                     riab.HeadDirectionCells(ag, {"n": 4, "save_spikes": False}))
+
+    def native(make_pop, calls, configure=()):
+        """a warm call, then one simulate() per entry of `calls`, each from an idle stream: the rows and the agent"""
+        os.environ["RIAB_NO_FUSED"] = os.environ["RIAB_NO_NATIVE"] = "0"
+        try:
+            _env, ag, pop = _world(riab, 256, make_pop)
+            ag.simulate(4)
+            for option, value in configure:
+                L.check(L.lib.riab_streamer_configure(ag._streamer, option, value), "configure")
+            for T, (form, strict, launches) in calls:
+                torch.cuda.synchronize()
+                ag.simulate(T)
+                info = ag.pipeline_info()
+                got = (ag.last_rate_stage_form(), info["strict_last_call"], info["launches_last_call"])
+                assert got == (names[form], bool(strict), launches), (T, configure, got)
+            torch.cuda.synchronize()
+            assert ag.diagnostics["pipeline_timeouts"] == 0
+            fr, sp = pop.get_history_tensors()
+            return ag.get_history_tensor().cpu().numpy(), fr.cpu().numpy(), sp.cpu().numpy()
+        finally:
+            os.environ.pop("RIAB_NO_FUSED", None)
+            os.environ.pop("RIAB_NO_NATIVE", None)
+
+    one = _pc(8, save_spikes=False)
+    got = native(one, [(T, expect) for T, _facts, expect in REAL_CALLS_ONE])
+    ref = _run(riab, False, 256, one, [("sim", 4)] + [("sim", T) for T, _facts, _expect in REAL_CALLS_ONE])
+    for x, y in zip(got, ref[:3]):
+        np.testing.assert_array_equal(x, y)
+    ref = _run(riab, False, 256, two, [("sim", 4), ("sim", 33)])
+    options = {"step_ns_cfg": L.STREAMER_OPT_STEP_NS, "lead_mbps_cfg": L.STREAMER_OPT_LEAD_MBPS}
+    for facts, expect in REAL_CALLS_TWO:
+        configure = [(options[k], int(v)) for k, v in (w.split("=") for w in facts.split())]
+        got = native(two, [(33, expect)], configure)
+        for x, y in zip(got, ref[:3]):
+            np.testing.assert_array_equal(x, y)
+
+
 
 def test_aborted_pipeline_flags_are_settled_on_the_next_host_read(riab):
     """A wait that gave up (here: the abort / timeout words set by hand after complete runs) must not pass silently:
