@@ -25,11 +25,11 @@
 #include "riab_act.h"
 #include "riab_device.h"
 #include "riab_mfma_slab.h"   // v4f, v16f, KT, swizzle()
+#include "riab_mlp_logic.h"   // MLP_MAX_INPUTS, MLP_A_FLOATS; what the host decides per call (mlp_decide)
 
 namespace riab {
 
-constexpr int MLP_MAX_INPUTS = 8;
-constexpr int MLP_A_FLOATS = 2 * (KT / 4) * 128 * 4;  // LDS: W slab [buf][rg][row][s], 16 KB; behind it the rates slab
+static_assert(MLP_KT == KT, "riab_mlp_logic.h sizes the LDS slabs for riab_mfma_slab.h's KT");
 
 struct MLPLayerArgs {
   const float* w;     // [n_out][n_in]
@@ -272,6 +272,7 @@ __global__ __launch_bounds__(256) void mlp_kernel(const MLPArgs a) {
     for (int pass = 0; pass < n_pass; ++pass) {
       const int m0 = pass << 7, left = L.n_out - m0;
       v16f acc[MAXT];
+      // (this choice of MT is restated for the host's record as mlp_pass_mt in riab_mlp_logic.h: change both together)
       if constexpr (MAXT == 4) {
         if (left > 64) mlp_first_layer<4, MAXT>(a, mlp_smem, m0, t, b0, nw, acc);
         else if (left > 32) mlp_first_layer<2, MAXT>(a, mlp_smem, m0, t, b0, nw, acc);
@@ -295,7 +296,7 @@ __global__ __launch_bounds__(256) void mlp_kernel(const MLPArgs a) {
   for (int l = 1; l < n_layers; ++l) {
     const MLPLayerArgs& L = a.layer[l];
     const bool last = l == n_layers - 1;
-    const int mti = (L.n_in + 31) >> 5;  // 1..MAXT
+    const int mti = (L.n_in + 31) >> 5;  // 1..MAXT  (restated as mlp_mti in riab_mlp_logic.h: change both together)
     v16f hn[MAXT];
     for (int m0 = 0; m0 < L.n_out; m0 += 32) {  // (only the last layer has more than MAXT tiles)
       v16f acc;
@@ -355,29 +356,33 @@ using namespace riab;
 extern "C" int riab_mlp_forward(const float* const* inputs, const int32_t* input_n, int32_t n_inputs,
                                 const RiabMLPLayer* layers, int32_t n_layers, int64_t T, int64_t B, float* out,
                                 riab_stream_t stream) {
-  if (!inputs || !input_n || !layers || !out || n_inputs <= 0 || n_layers <= 0 || T <= 0 || B <= 0) return RIAB_EINVAL;
-  if (n_inputs > MLP_MAX_INPUTS || n_layers > RIAB_MLP_MAX_LAYERS || T > 65535) return RIAB_ETOOBIG;
+  if (!inputs || !input_n || !layers) return RIAB_EINVAL;
+  // the facts (entries past the limits are not read: mlp_validate refuses such a call by its counts) ...
+  MLPFacts f = {};
+  f.n_inputs = n_inputs;
+  f.n_layers = n_layers;
+  for (int l = 0; l < n_inputs && l < MLP_MAX_INPUTS; ++l)
+    f.in[l] = MLPInputFacts{input_n[l], inputs[l] == nullptr, (unsigned)((uintptr_t)inputs[l] & 15)};
+  for (int i = 0; i < n_layers && i < RIAB_MLP_MAX_LAYERS; ++i) {
+    const RiabMLPLayer& q = layers[i];
+    f.layer[i] = MLPLayerFacts{q.n_in, q.n_out, q.activation, q.w == nullptr, q.bias != nullptr, (unsigned)((uintptr_t)q.w & 15)};
+  }
+  f.T = T;
+  f.B = B;
+  f.out_null = out == nullptr;
+  f.out_mod16 = (unsigned)((uintptr_t)out & 15);
+  f.cus = mlp_compute_units();
+  // ... the decision (riab_mlp_logic.h: every check and every choice of form is there) ...
+  const MLPDecision d = mlp_decide(f);
+  if (d.rc != RIAB_OK) return d.rc;
+  // ... and its launch
   MLPArgs a;
-  int64_t k_sum = 0;
   for (int l = 0; l < n_inputs; ++l) {
-    if (!inputs[l] || input_n[l] <= 0) return RIAB_EINVAL;
     a.rates[l] = inputs[l];
     a.n[l] = input_n[l];
-    a.koff[l] = (int)k_sum;
-    k_sum += input_n[l];
+    a.koff[l] = d.koff[l];
+    a.vec0[l] = d.vec0[l];
   }
-  for (int i = 0; i < n_layers; ++i) {
-    const RiabMLPLayer& q = layers[i];
-    if (!q.w || q.n_in <= 0 || q.n_out <= 0) return RIAB_EINVAL;
-    if (q.activation < RIAB_ACT_LINEAR || q.activation > RIAB_ACT_SOFTMAX) return RIAB_EINVAL;
-    if (i > 0 && q.n_in != layers[i - 1].n_out) return RIAB_EINVAL;
-  }
-  if (k_sum != (int64_t)layers[0].n_in) return RIAB_EINVAL;
-  for (int i = 0; i + 1 < n_layers; ++i)
-    if (layers[i].n_out > RIAB_MLP_MAX_HIDDEN) return RIAB_ETOOBIG;
-  if (B % 4 != 0 || ((uintptr_t)out & 15)) return RIAB_EALIGN;
-  for (int l = 0; l < n_inputs; ++l)
-    if ((uintptr_t)inputs[l] & 15) return RIAB_EALIGN;
   for (int i = 0; i < n_layers; ++i) {
     const RiabMLPLayer& q = layers[i];
     MLPLayerArgs& L = a.layer[i];
@@ -386,27 +391,19 @@ extern "C" int riab_mlp_forward(const float* const* inputs, const int32_t* input
     L.n_in = q.n_in;
     L.n_out = q.n_out;
     L.act = q.activation;
-    // a row of w starts on a 16-byte boundary only when the base does and n_in % 4 == 0: 16-byte reads then, 4-byte otherwise
-    L.vec = (((uintptr_t)q.w & 15) == 0 && q.n_in % 4 == 0) ? 1 : 0;
+    L.vec = d.vec[i];
     L.p0 = q.act_params[0];
     L.p1 = q.act_params[1];
     L.p2 = q.act_params[2];
     L.p3 = q.act_params[3];
   }
-  for (int l = 0; l < n_inputs; ++l) a.vec0[l] = (a.layer[0].vec && a.koff[l] % 4 == 0) ? 1 : 0;
   a.n_inputs = n_inputs;
   a.n_layers = n_layers;
   a.B = B;
   a.out = out;
-  const int64_t wide = (B + 127) / 128 * T;
-  const int nw = wide >= mlp_compute_units() ? 4 : 1;
-  const dim3 grid((unsigned)((B + nw * 32 - 1) / (nw * 32)), 1, (unsigned)T);
-  const size_t smem = (size_t)(MLP_A_FLOATS + 2 * (KT / 4) * (nw * 32) * 4) * sizeof(float);
-  // the widest activation carried in registers: every hidden width, or the only layer's rows of one pass
-  int widest = n_layers == 1 ? (layers[0].n_out < 128 ? layers[0].n_out : 128) : 0;
-  for (int i = 0; i + 1 < n_layers; ++i) widest = layers[i].n_out > widest ? layers[i].n_out : widest;
-  if (widest > 64) hipLaunchKernelGGL(mlp_kernel<4>, grid, dim3(64 * nw), smem, (hipStream_t)stream, a);
-  else if (widest > 32) hipLaunchKernelGGL(mlp_kernel<2>, grid, dim3(64 * nw), smem, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(mlp_kernel<1>, grid, dim3(64 * nw), smem, (hipStream_t)stream, a);
+  const dim3 grid(d.grid_x, 1, d.grid_z), block(64 * d.nw);
+  if (d.maxt == 4) hipLaunchKernelGGL(mlp_kernel<4>, grid, block, d.lds_bytes, (hipStream_t)stream, a);
+  else if (d.maxt == 2) hipLaunchKernelGGL(mlp_kernel<2>, grid, block, d.lds_bytes, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(mlp_kernel<1>, grid, block, d.lds_bytes, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }

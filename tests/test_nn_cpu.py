@@ -58,6 +58,33 @@ def test_oracle_sequential_has_a_bias_free_layer():
     assert "p::2.weight" in g and "p::2.bias" not in g and "p::0.bias" in g
 
 
+# (code, p0, p1, p2, p3) off the defaults: RIAB_ACT_* sigmoid, relu, tanh, retanh, softplus, and linear (which ignores them)
+CODED = [(1, 2.0, -0.5, 0.3, 1.7), (1, -1.0, 2.0, -0.4, -3.0), (2, 1.5, 0.2, 0.0, 0.0), (2, -0.7, -0.3, 0.0, 0.0),
+         (3, 0.8, -0.1, 0.0, 0.0), (4, 1.3, 0.15, 0.0, 0.0), (5, 0.6, -0.3, 0.0, 0.0), (5, -2.5, 0.4, 0.0, 0.0),
+         (0, 3.0, 1.0, 0.5, 2.0)]
+
+
+@pytest.mark.parametrize("act", CODED, ids=lambda a: "-".join(str(v) for v in a))
+def test_lipschitz_constants_by_finite_differences(act):
+    """nn_oracle.lipschitz for the kernel's (code, p0..p3): no float64 central difference on a fine grid exceeds it, and
+    the largest comes within 1 % of it (the constant is the supremum, not merely a bound)."""
+    lip = nn_oracle.lipschitz(act)
+    x = np.linspace(-40.0, 40.0, 800001)          # 1e-4 apart: the retanh supremum sits just right of its threshold
+    h = 1e-6
+    slope = np.abs(nn_oracle.activate(act, x + h) - nn_oracle.activate(act, x - h)) / (2 * h)
+    assert slope.max() <= lip * (1 + 1e-6), (slope.max(), lip)
+    assert slope.max() >= 0.99 * lip, (slope.max(), lip)
+
+
+def test_coded_activations_at_their_defaults_are_the_named_ones():
+    x = np.linspace(-30.0, 30.0, 6001)
+    for name, code, pars in (("linear", 0, (0.0, 0.0, 0.0, 0.0)), ("sigmoid", 1, (1.0, 0.0, 0.0, 1.0)), ("relu", 2, (1.0, 0.0, 0.0, 0.0)),
+                             ("tanh", 3, (1.0, 0.0, 0.0, 0.0)), ("softplus", 5, (1.0, 0.0, 0.0, 0.0))):
+        assert np.array_equal(nn_oracle.activate((code,) + pars, x), nn_oracle.activate(name, x)), name
+        assert nn_oracle.lipschitz((code,) + pars) == nn_oracle.LIP[name]
+    assert np.array_equal(nn_oracle.activate((4, 1.0, 0.0, 0.0, 0.0), x), np.maximum(np.tanh(x), 0.0))
+
+
 # ----------------------------------------------------------------------------------------------- constructor
 def test_n_from_the_module_and_n_in(riab, nnn):
     N = _make(riab, nnn, nn.Sequential(nn.Linear(50, 7)))
