@@ -1469,6 +1469,55 @@ int riab_bayes_filter(const float* loglik, int64_t W, int32_t J, int32_t Jp, int
                       const float* centres, const uint8_t* restart, int32_t first, float* post, float* tmp,
                       float* workspace, float* out, riab_stream_t stream);
 
+/* riab_bayes_filter with every window's l kept (a new export at ABI 11): window w writes and re-reads its l at
+ * ells + w Jp B where riab_bayes_filter goes through post; the same two kernels, the same arithmetic, the same bits in out,
+ * tmp and the workspace, and ells[W - 1] holds what post would.  The backward smoother reads them.
+ *   ells        device float32 [W][Jp][B], 16-byte aligned; padding bins j >= J are written (-inf)
+ * Every other argument, the launches and the checks are riab_bayes_filter's, with ells in post's place. */
+int riab_bayes_filter_keep(const float* loglik, int64_t W, int32_t J, int32_t Jp, int32_t ny, int32_t nx, int64_t B,
+                           int32_t radius, const float* taps, float mixing, const float* prior, const float* inv_norm,
+                           const float* centres, const uint8_t* restart, int32_t first, float* ells, float* tmp,
+                           float* workspace, float* out, riab_stream_t stream);
+
+/* ---- The backward smoother behind that filter: p(x_t | k_1..k_T) of a recorded run ---------------------------------------
+ * (csrc/riab_bayes_smooth.hip; a new export at ABI 11: no struct, enum value or existing signature changes.)
+ * With ev_t = filtered[t][4] = log p(k_t | k_<t), p_t(j) = exp(ells[t][j] - ev_t), beta of the run's last window 1 and t
+ * descending:
+ *   u_{t+1}(j) = exp(loglik[t+1][j] - ev_{t+1}) beta_{t+1}(j)                      0 where j is not admissible
+ *   c_t        = sum_j prior_j u_{t+1}(j)
+ *   beta_t(j') = (1 - mixing) inv_norm_j' sum_j G(j - j') u_{t+1}(j) + mixing c_t ok_j'
+ *   gamma_t(j) = p_t(j) beta_t(j) / sum_i p_t(i) beta_t(i)
+ * (sum_i p_t beta_t = 1 in exact arithmetic and beta <= 1 / (mixing min prior): nothing is rescaled per window).  The chain
+ * is cut at window t — beta_t = 1 and out[t] is filtered[t], copied bit for bit — when t is the last window of a call with
+ * last != 0, when restart[t + 1] is set, or when filtered[t + 1][4] or filtered[t][4] is NaN.  Otherwise out[t] = the mean of
+ * gamma_t (x, y); the centre of its MAP bin (x, y; the LOWEST j among the maxima); filtered[t][4] unchanged; gamma_t at the
+ * MAP bin.
+ *   loglik      device float32 [W][Jp][B], what riab_bayes_filter_keep was given for these windows
+ *   ells        device float32 [W][Jp][B], what it wrote; bins j >= J are not read
+ *   filtered    device float32 [W][RIAB_BAYES_OUT_ROWS][B], its outputs (not out)
+ *   taps, prior, inv_norm, centres, restart [W][B] or NULL: as riab_bayes_filter takes them
+ *   last        non-zero: the call's last window is the run's last (beta, tmp and the workspace hold nothing); 0: the call
+ *               continues, to the LEFT, the run whose later windows the last call smoothed: a run is given rightmost first
+ *   beta, tmp   device float32 [Jp][B] each: beta of the call's first window and the x-blur of its u; the state between calls
+ *   workspace   device, RIAB_BAYES_SMOOTH_WORKSPACE_FLOATS(Jp, B) float32: S partial states of gamma [S][5][B], the
+ *               ceil(S / 4) partials of c (one per workgroup of the u stage) and one 32-bit cut flag per column,
+ *               S = RIAB_BAYES_FILTER_SPLITS(Jp); part of the state between calls
+ *   out         device float32 [W][RIAB_BAYES_OUT_ROWS][B]
+ * 2 W launches in order on the stream, windows W - 1 .. 0 (smooth_gamma_kernel, smooth_u_kernel per window).  Fixed order,
+ * no atomics; the split of the bins depends on Jp alone and columns are independent: a column's bits depend on neither B
+ * nor its neighbours, and a call of W windows has the bits of W calls of one window, rightmost first.  Padding bins j >= J
+ * of beta / tmp are written (0).  W = 0 launches nothing.
+ * Checked before anything is launched: RIAB_EINVAL null pointers (restart may be NULL), W < 0, J < 1, Jp < J, ny nx != J,
+ * B < 1, radius outside 1..RIAB_BAYES_FILTER_MAX_RADIUS, mixing outside (0, 1], a tap outside [0, 1]; RIAB_EUNSUPPORTED
+ * J > RIAB_RATEMAP_MAX_BINS; RIAB_EALIGN B % 4, Jp % 32 or a pointer that is not 16-byte aligned (restart: any);
+ * RIAB_ETOOBIG W > 65535 or ceil(B / 64) >= 2^31. */
+#define RIAB_BAYES_SMOOTH_WORKSPACE_FLOATS(Jp, B) \
+  ((5 * (int64_t)RIAB_BAYES_FILTER_SPLITS(Jp) + (RIAB_BAYES_FILTER_SPLITS(Jp) + 3) / 4 + 1) * (int64_t)(B))
+int riab_bayes_smooth(const float* loglik, const float* ells, const float* filtered, int64_t W, int32_t J, int32_t Jp,
+                      int32_t ny, int32_t nx, int64_t B, int32_t radius, const float* taps, float mixing, const float* prior,
+                      const float* inv_norm, const float* centres, const uint8_t* restart, int32_t last, float* beta,
+                      float* tmp, float* workspace, float* out, riab_stream_t stream);
+
 /* sizeof of the ABI's structs as compiled into the library (which: 0 RiabEnv, 1 RiabMotion, 2 RiabRateIO,
  * 3 RiabPopulation, 4 RiabTask, 5 RiabFFInput, 7 RiabSimulate, 8 RiabWatch, 9 RiabTDParams, 10 RiabTDLayer, 11 RiabMLPLayer, 12 RiabMomentInput; 6 returns RIAB_TS_ROWS): bindings verify their mirrors at
  * load */

@@ -42,10 +42,10 @@ from .Neurons import (  # noqa: E402,F401
     RandomSpatialNeurons, FeedForwardLayer)
 from ._decoder import LinearDecoder, fit_linear_decoder, history_moments_tensor  # noqa: E402,F401
 from ._gp_decoder import GPDecoder, fit_gp_decoder  # noqa: E402,F401
-from ._bayes_decoder import BayesianDecoder, BayesianFilter, fit_bayesian_decoder  # noqa: E402,F401
+from ._bayes_decoder import BayesianDecoder, BayesianFilter, BayesianSmoother, fit_bayesian_decoder  # noqa: E402,F401
 
 __all__ = ["Environment", "Agent", "Neurons", "PlaceCells", "GridCells", "VectorCells", "BoundaryVectorCells",
            "FieldOfViewBVCs", "ObjectVectorCells", "FieldOfViewOVCs", "AgentVectorCells", "FieldOfViewAVCs",
            "HeadDirectionCells", "VelocityCells", "SpeedCell", "RandomSpatialNeurons", "FeedForwardLayer",
            "LinearDecoder", "fit_linear_decoder", "history_moments_tensor", "GPDecoder", "fit_gp_decoder",
-           "BayesianDecoder", "BayesianFilter", "fit_bayesian_decoder", "utils"]
+           "BayesianDecoder", "BayesianFilter", "BayesianSmoother", "fit_bayesian_decoder", "utils"]

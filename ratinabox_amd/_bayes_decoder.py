@@ -17,7 +17,11 @@ sample it returns the posterior mean, the MAP bin's centre, the log evidence and
 `BayesianDecoder.with_continuity()` adds the continuity prior of the literature (Zhang et al. 1998): `BayesianFilter` carries
 the posterior of a window to the next through a Gaussian step over the admissible bins, as a causal forward filter.  The
 likelihood of a batch of windows is `torch.ops.riab.feedforward` on the same tables, the scan over the windows
-`torch.ops.riab.bayes_filter` (csrc/riab_bayes_filter.hip): two kernels per window issued by one native call."""
+`torch.ops.riab.bayes_filter` (csrc/riab_bayes_filter.hip): two kernels per window issued by one native call.
+
+`BayesianFilter.smoothed()` puts a backward pass behind that filter (`BayesianSmoother`): the history is a recorded run, so
+window t can be decoded from every window of the run, p(x_t | k_1..k_T).  The forward pass keeps the log posterior of every
+window (`torch.ops.riab.bayes_filter_keep`), the backward scan is `torch.ops.riab.bayes_smooth` (csrc/riab_bayes_smooth.hip)."""
 import numpy as np
 import torch
 
@@ -321,11 +325,23 @@ class BayesianFilter(HistoryDecoder):
         counts), filtered forward from the first: float32 `[T'][6][Bp]`, rows as there except that row 4 is the predictive log
         likelihood log p(k_t | k_<t).  `restart`: a bool tensor or array (T', B) — or (T', Bp) —; a set flag starts that
         agent's filter afresh at that window (episode ends, the edges of a ReplayAgent's history["replay"])."""
+        agent, window, n_windows, flags, runs = self._runs(t_start, t_end, window, inputs, restart)
+        if n_windows == 0:
+            return torch.empty((0, _L.BAYES_OUT_ROWS, agent._Bp), dtype=torch.float32, device=agent._device)
+        parts, state = [], None
+        for x, w0, n in runs:
+            out, state = self.filter_inputs_tensor(x, window, None if flags is None else flags[w0:w0 + n], state)
+            parts.append(out)
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+    def _runs(self, t_start, t_end, window, inputs, restart):
+        """(agent, window, n_windows, restart flags uint8 (T', Bp) or None, [(inputs of consecutive windows, their first
+        window, how many)]) of a decode: the windows `BayesianDecoder.decode_all_tensor` decodes, piece by piece"""
         dec = self.decoder
         agent, hists, _start, window, n_windows, pieces = dec._windows(t_start, t_end, window, inputs)
         dev, Bp = agent._device, agent._Bp
         if n_windows == 0:
-            return torch.empty((0, _L.BAYES_OUT_ROWS, Bp), dtype=torch.float32, device=dev)
+            return agent, window, 0, None, []
         flags = None
         if restart is not None:
             r = torch.as_tensor(np.asarray(restart) if not torch.is_tensor(restart) else restart).to(dev)
@@ -341,11 +357,7 @@ class BayesianFilter(HistoryDecoder):
                 for h, (c, r), cnt in zip(hists, first, counts):
                     torch.ops.riab.history_window_counts(h.chunks[c][r:r + length], row0, window, cnt)
             runs = [(counts, 0, n_windows)]
-        parts, state = [], None
-        for x, w0, n in runs:
-            out, state = self.filter_inputs_tensor(x, window, None if flags is None else flags[w0:w0 + n], state)
-            parts.append(out)
-        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+        return agent, window, n_windows, flags, runs
 
     def decode_tensor(self, t_start=None, t_end=None, window=None, inputs="spikes", estimate="mean", restart=None):
         """The filtered position of every window: float32 `[T'][2][Bp]`, the posterior mean (estimate="mean") or the MAP
@@ -357,6 +369,137 @@ class BayesianFilter(HistoryDecoder):
 
     def _target_tensor(self, t_start, t_end):
         return self.decoder._target_tensor(t_start, t_end)
+
+    def smoothed(self, max_state_bytes=2 ** 31):
+        """This filter followed by a backward pass over the recorded run (`BayesianSmoother`): every window is decoded from
+        ALL the windows of its run, not only from those up to it.  `max_state_bytes`: what the smoother may keep on the
+        device between the two passes."""
+        return BayesianSmoother(self, max_state_bytes)
+
+
+class BayesianSmoother(HistoryDecoder):
+    """A `BayesianFilter` run forward and then backward over a recorded run (forward-backward smoothing): the posterior of
+    window t given every window of the run, p(x_t | k_1..k_T), where the filter gives p(x_t | k_1..k_t).  The forward pass is
+    the filter's with the log posterior l_t of every window kept (`torch.ops.riab.bayes_filter_keep`); the backward pass
+    (`torch.ops.riab.bayes_smooth`, csrc/riab_bayes_smooth.hip: two kernels per window issued by one native call per batch)
+    carries beta_t(j) ~ p(k_t+1..k_T | x_t = j) from the last window to the first and never crosses a restart or a NaN window,
+    as the filter never does.  Rows of the outputs as the filter's; row 4 is the filter's, log p(k_t | k_<t).
+
+    Between the passes the l of every window stays on the device, float32 (T', Jp, Bp), and so does the log likelihood when
+    both fit in `max_state_bytes`; when they do not, the log likelihood is recomputed batch by batch on the way back, and when
+    l alone does not fit either, the agents are run in blocks of a multiple of 64 columns that do.  Columns are independent:
+    the blocks have the bits of one block."""
+
+    target = "pos"
+
+    def __init__(self, filt, max_state_bytes=2 ** 31):
+        if isinstance(max_state_bytes, bool) or int(max_state_bytes) != max_state_bytes or int(max_state_bytes) < 1:
+            raise ValueError(f"max_state_bytes must be a positive integer, got {max_state_bytes}")
+        self.filter, self.decoder, self.max_state_bytes = filt, filt.decoder, int(max_state_bytes)
+        self.window = filt.window
+
+    def _populations(self):
+        return self.decoder._populations()
+
+    def _target_tensor(self, t_start, t_end):
+        return self.decoder._target_tensor(t_start, t_end)
+
+    def column_blocks(self, n_windows, Bp):
+        """(whether the log likelihood is kept, [(first column, end)]) of a run of `n_windows` windows over `Bp` columns"""
+        Jp = int(self.decoder.S.shape[0])
+        per_column = 4 * int(n_windows) * Jp                     # the l of every window, one column
+        if 2 * per_column * Bp <= self.max_state_bytes:
+            return True, [(0, Bp)]
+        if per_column * Bp <= self.max_state_bytes:
+            return False, [(0, Bp)]
+        cols = self.max_state_bytes // per_column // 64 * 64
+        if cols < 64:
+            raise ValueError(f"smoothing {n_windows} windows over {Jp} bins keeps {per_column * min(64, Bp)} bytes for a block of "
+                             f"{min(64, Bp)} agents, max_state_bytes is {self.max_state_bytes}: raise it, or smooth fewer "
+                             "windows at a time")
+        return False, [(c, min(c + cols, Bp)) for c in range(0, Bp, cols)]
+
+    def _smooth_block(self, runs, window, flags, keep_loglik):
+        """Forward, then backward, over the runs' windows for the columns the tensors hold -> float32 (T', 6, B)"""
+        filt, dec = self.filter, self.decoder
+        dev, B, Jp = runs[0][0][0].device, int(runs[0][0][0].shape[2]), int(dec.S.shape[0])
+        tau = np.float32(_check_window(window) * dec.dt)
+        bias = filt._lik_bias(window)
+        ny, nx = filt.grid_shape
+        tables = (filt._taps32, filt.mixing, filt.prior, filt.inv_norm, dec.centres)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        step = max(1, min(65535, FILTER_LOGLIK_BYTES // (4 * Jp * B)))
+        if filt._max_windows_per_call is not None:
+            step = max(1, min(step, int(filt._max_windows_per_call)))
+
+        def loglik_of(xs, o):
+            x = [t[o:o + step].to(torch.float32) if t.dtype == torch.uint8 else t[o:o + step] * float(tau) for t in xs]
+            return torch.ops.riab.feedforward(x, dec.log_rates, bias, _L.ACTIVATIONS["linear"], [0.0, 0.0, 0.0, 0.0])
+
+        tmp, ws = new(Jp, B), new(_ops.bayes_filter_workspace_floats(Jp, B))
+        batches = []                                             # (inputs, offset, l, the filter's outputs, loglik, flags)
+        for xs, w0, n in runs:
+            for o in range(0, n, step):
+                loglik = loglik_of(xs, o)
+                m = int(loglik.shape[0])
+                ells, filtered = new(m, Jp, B), new(m, _L.BAYES_OUT_ROWS, B)
+                fl = None if flags is None else flags[w0 + o:w0 + o + m]
+                torch.ops.riab.bayes_filter_keep(loglik, dec.n_bins, ny, nx, *tables, fl, not batches, ells, tmp, ws, filtered)
+                batches.append((xs, o, ells, filtered, loglik if keep_loglik else None, fl))
+        beta, ws = new(Jp, B), new(_ops.bayes_smooth_workspace_floats(Jp, B))
+        outs = [None] * len(batches)
+        for i in reversed(range(len(batches))):
+            xs, o, ells, filtered, loglik, fl = batches[i]
+            batches[i] = None
+            outs[i] = torch.empty_like(filtered)
+            torch.ops.riab.bayes_smooth(loglik_of(xs, o) if loglik is None else loglik, ells, filtered, dec.n_bins, ny, nx, *tables,
+                                        fl, i == len(outs) - 1, beta, tmp, ws, outs[i])
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+    def _smooth_runs(self, runs, window, flags, n_windows, Bp):
+        keep, blocks = self.column_blocks(n_windows, Bp)
+        if len(blocks) == 1:
+            return self._smooth_block(runs, window, flags, keep)
+        out = torch.empty((n_windows, _L.BAYES_OUT_ROWS, Bp), dtype=torch.float32, device=runs[0][0][0].device)
+        for c0, c1 in blocks:
+            part = [([x[:, :, c0:c1].contiguous() for x in xs], w0, n) for xs, w0, n in runs]
+            out[:, :, c0:c1] = self._smooth_block(part, window, None if flags is None else flags[:, c0:c1].contiguous(), keep)
+        return out
+
+    def smooth_inputs_tensor(self, inputs, window=1, restart=None):
+        """The smoother over inputs that are not in a history, as `BayesianFilter.filter_inputs_tensor` takes them: a list of
+        uint8 count or float32 rate tensors `[T][n_l][Bp]`, the consecutive windows of ONE run, all of it -> float32
+        `[T][6][Bp]`.  `restart`: bool or uint8 tensor (T, Bp) or None."""
+        dec = self.decoder
+        inputs = list(inputs)
+        if len(inputs) != len(dec.widths) or any(int(x.shape[1]) != w for x, w in zip(inputs, dec.widths)):
+            raise ValueError(f"this decoder takes {len(dec.widths)} input tensors (T, n_l, Bp) of widths {dec.widths}")
+        T, Bp = int(inputs[0].shape[0]), int(inputs[0].shape[2])
+        if T == 0:
+            return torch.empty((0, _L.BAYES_OUT_ROWS, Bp), dtype=torch.float32, device=inputs[0].device)
+        flags = None
+        if restart is not None:
+            if tuple(restart.shape) != (T, Bp):
+                raise ValueError(f"restart must be ({T}, {Bp}): one flag per window and column, got {tuple(restart.shape)}")
+            flags = (restart != 0).to(torch.uint8).contiguous()
+        return self._smooth_runs([(inputs, 0, T)], window, flags, T, Bp)
+
+    def decode_all_tensor(self, t_start=None, t_end=None, window=None, inputs="spikes", restart=None):
+        """Every output of the consecutive windows `BayesianFilter.decode_all_tensor` decodes (the same rows, the same counts,
+        the same `restart`), smoothed over the whole run: float32 `[T'][6][Bp]`, rows 0-1 the smoothed posterior mean, 2-3
+        the centre of the smoothed MAP bin, 4 the filter's log p(k_t | k_<t), 5 the smoothed MAP probability."""
+        agent, window, n_windows, flags, runs = self.filter._runs(t_start, t_end, window, inputs, restart)
+        if n_windows == 0:
+            return torch.empty((0, _L.BAYES_OUT_ROWS, agent._Bp), dtype=torch.float32, device=agent._device)
+        return self._smooth_runs(runs, window, flags, n_windows, agent._Bp)
+
+    def decode_tensor(self, t_start=None, t_end=None, window=None, inputs="spikes", estimate="mean", restart=None):
+        """The smoothed position of every window: float32 `[T'][2][Bp]`, the posterior mean (estimate="mean") or the MAP
+        bin's centre ("map")."""
+        if estimate not in ("mean", "map"):
+            raise ValueError(f"estimate must be 'mean' or 'map', got {estimate!r}")
+        lo = OUT_ROWS[estimate][0]
+        return self.decode_all_tensor(t_start, t_end, window, inputs, restart)[:, lo:lo + 2]
 
 
 def _check_window(window):

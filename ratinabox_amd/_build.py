@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libriab_hip.so")
 SOURCES = ["riab_rates.hip", "riab_agent.hip", "riab_bvc.hip", "riab_ff.hip", "riab_ovc.hip", "riab_plan.hip",
            "riab_task.hip", "riab_task_world.hip", "riab_env.hip", "riab_simulate.hip", "riab_step1.hip", "riab_td.hip",
            "riab_theta_seq.hip", "riab_subagent.hip", "riab_ratemap.hip", "riab_mlp.hip", "riab_decoder.hip", "riab_gp.hip",
-           "riab_bayes.hip", "riab_bayes_filter.hip"]
+           "riab_bayes.hip", "riab_bayes_filter.hip", "riab_bayes_smooth.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 
 

@@ -29,6 +29,9 @@
 // The number of splits is a function of Jp alone and a lane's arithmetic touches its own column only: a column's bits depend
 // on neither B, the tile nor its neighbours, and whatever a padding lane holds stays in its column.  No atomics; every word
 // of post, tmp, the workspace and out has one owner per launch.  Padding bins J..Jp-1 are written (-inf / 0), never read.
+//
+// riab_bayes_filter_keep is the same scan with every window's l kept: window w goes through ells[w] where riab_bayes_filter
+// goes through post.  The backward smoother (riab_bayes_smooth.hip) reads them.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -243,12 +246,12 @@ __global__ __launch_bounds__(256) void filter_blur_kernel(const FilterArgs a) {
   }
 }
 
-}  // namespace
-
-extern "C" int riab_bayes_filter(const float* loglik, int64_t W, int32_t J, int32_t Jp, int32_t ny, int32_t nx, int64_t B,
-                                 int32_t radius, const float* taps, float mixing, const float* prior, const float* inv_norm,
-                                 const float* centres, const uint8_t* restart, int32_t first, float* post, float* tmp,
-                                 float* workspace, float* out, riab_stream_t stream) {
+// The checks and the launches of both exports.  `ells` null: every window's l goes through post; else window w's goes through
+// ells + w Jp B (written by filter_post_kernel, re-read by filter_blur_kernel: the same two kernels on another address).
+static int filter_run(const float* loglik, int64_t W, int32_t J, int32_t Jp, int32_t ny, int32_t nx, int64_t B, int32_t radius,
+                      const float* taps, float mixing, const float* prior, const float* inv_norm, const float* centres,
+                      const uint8_t* restart, int32_t first, float* post, float* ells, float* tmp, float* workspace, float* out,
+                      riab_stream_t stream) {
   if (!loglik || !taps || !prior || !inv_norm || !centres || !post || !tmp || !workspace || !out) return RIAB_EINVAL;
   if (W < 0 || J < 1 || Jp < J || ny < 1 || nx < 1 || B <= 0) return RIAB_EINVAL;
   if ((int64_t)ny * nx != J) return RIAB_EINVAL;
@@ -285,6 +288,7 @@ extern "C" int riab_bayes_filter(const float* loglik, int64_t W, int32_t J, int3
   const dim3 grid_post((unsigned)tiles, (unsigned)a.S), grid_blur((unsigned)tiles, (unsigned)((a.S + 3) / 4));
   for (int64_t w = 0; w < W; ++w) {
     a.loglik = loglik + w * Jp * B;
+    if (ells) a.post = ells + w * Jp * B;
     a.restart = restart ? restart + w * B : nullptr;
     a.out = out + w * RIAB_BAYES_OUT_ROWS * B;
     a.all_fresh = (first && w == 0) ? 1 : 0;
@@ -294,4 +298,23 @@ extern "C" int riab_bayes_filter(const float* loglik, int64_t W, int32_t J, int3
     if (rc) return rc;
   }
   return RIAB_OK;
+}
+
+}  // namespace
+
+extern "C" int riab_bayes_filter(const float* loglik, int64_t W, int32_t J, int32_t Jp, int32_t ny, int32_t nx, int64_t B,
+                                 int32_t radius, const float* taps, float mixing, const float* prior, const float* inv_norm,
+                                 const float* centres, const uint8_t* restart, int32_t first, float* post, float* tmp,
+                                 float* workspace, float* out, riab_stream_t stream) {
+  return filter_run(loglik, W, J, Jp, ny, nx, B, radius, taps, mixing, prior, inv_norm, centres, restart, first, post, nullptr,
+                    tmp, workspace, out, stream);
+}
+
+extern "C" int riab_bayes_filter_keep(const float* loglik, int64_t W, int32_t J, int32_t Jp, int32_t ny, int32_t nx, int64_t B,
+                                      int32_t radius, const float* taps, float mixing, const float* prior,
+                                      const float* inv_norm, const float* centres, const uint8_t* restart, int32_t first,
+                                      float* ells, float* tmp, float* workspace, float* out, riab_stream_t stream) {
+  // (ells stands in post's place in the checks: null is RIAB_EINVAL, a misaligned one RIAB_EALIGN)
+  return filter_run(loglik, W, J, Jp, ny, nx, B, radius, taps, mixing, prior, inv_norm, centres, restart, first, ells, ells, tmp,
+                    workspace, out, stream);
 }

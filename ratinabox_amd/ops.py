@@ -21,6 +21,8 @@ Functional operators (return a new tensor)
 In-place operators
     history_window_counts  spike rows of a history piece added into the uint8 counts of their time windows
     bayes_filter     the Bayesian decoder with a continuity prior: a forward filter over consecutive windows, state carried
+    bayes_filter_keep  that filter with every window's log posterior kept; bayes_smooth: the backward pass over them, which
+                     turns the filtered posteriors of a recorded run into the smoothed ones
     history_moments  the float64 moment matrix of [rates ; targets ; 1] over history rows: what a ridge decoder is solved from
     td_forward_tail  the tail of ValueNeuron.update(): dV/dt, V_last and (optionally) the eligibility traces
     td_update        ValueNeuron.update_weights(reward): TD error, batch-mean gradient on the matrix cores, W^T updated
@@ -754,6 +756,41 @@ def bayes_filter_workspace_floats(Jp: int, B: int) -> int:
     return (5 * bayes_filter_splits(Jp) + 1) * B
 
 
+def bayes_smooth_workspace_floats(Jp: int, B: int) -> int:
+    """RIAB_BAYES_SMOOTH_WORKSPACE_FLOATS(Jp, B): the partial states of gamma [S][5][B], the ceil(S / 4) partials of c and
+    one 32-bit cut flag per column"""
+    S = bayes_filter_splits(Jp)
+    return (5 * S + (S + 3) // 4 + 1) * B
+
+
+def _bayes_scan_args(loglik, taps, tensors, workspace, n_ws, restart):
+    """The checks the scans over windows share -> (W, Jp, B, radius, the taps as a C array, restart as uint8 or None).
+    `tensors`: (name, tensor, shape with "W" / "Jp" / "B" for loglik's sizes)."""
+    if loglik.dtype != torch.float32 or loglik.dim() != 3 or not loglik.is_contiguous():
+        raise ValueError("loglik must be a contiguous float32 tensor (W, Jp, B)")
+    W, Jp, B = (int(x) for x in loglik.shape)
+    dev, size = loglik.device, {"W": W, "Jp": Jp, "B": B}
+    for name, t, shape in tensors:
+        shape = tuple(size.get(d, d) for d in shape)
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous float32 tensor {shape} on loglik's device")
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != dev or \
+            workspace.numel() < n_ws(Jp, B):
+        raise ValueError(f"workspace must be a contiguous float32 tensor of {n_ws(Jp, B)} elements")
+    if restart is not None:
+        if restart.dtype == torch.bool:
+            restart = restart.view(torch.uint8)
+        if restart.dtype != torch.uint8 or tuple(restart.shape) != (W, B) or not restart.is_contiguous() or restart.device != dev:
+            raise ValueError(f"restart must be a contiguous uint8 or bool tensor ({W}, {B}) on loglik's device")
+    radius = len(taps) - 1
+    if not 1 <= radius <= _L.BAYES_FILTER_MAX_RADIUS:
+        raise ValueError(f"taps must hold g[0..R] for a radius R in 1..{_L.BAYES_FILTER_MAX_RADIUS}, got {len(taps)} values")
+    return W, Jp, B, radius, (C.c_float * (radius + 1))(*[float(x) for x in taps]), restart
+
+
+_TABLES = (("prior", ("Jp",)), ("inv_norm", ("Jp",)), ("centres", (2, "Jp")))
+
+
 @_register("bayes_filter(Tensor loglik, int n_bins, int ny, int nx, float[] taps, float mixing, Tensor prior, Tensor inv_norm, "
            "Tensor centres, Tensor? restart, bool first, Tensor(a!) post, Tensor(b!) tmp, Tensor(c!) workspace, "
            "Tensor(d!) out) -> ()",
@@ -767,27 +804,58 @@ def bayes_filter(loglik: Tensor, n_bins: int, ny: int, nx: int, taps: List[float
     on a fresh column.  loglik float32 (W, Jp, B); taps R + 1 floats; prior, inv_norm float32 (Jp,); centres float32 (2, Jp);
     restart uint8 / bool (W, B) or None; first: a new run, else the state in post / tmp / workspace is continued; post, tmp
     float32 (Jp, B); workspace float32 of `bayes_filter_workspace_floats(Jp, B)` elements; out float32 (W, 6, B), written."""
-    if loglik.dtype != torch.float32 or loglik.dim() != 3 or not loglik.is_contiguous():
-        raise ValueError("loglik must be a contiguous float32 tensor (W, Jp, B)")
-    W, Jp, B = (int(x) for x in loglik.shape)
-    dev = loglik.device
-    for name, t, shape in (("prior", prior, (Jp,)), ("inv_norm", inv_norm, (Jp,)), ("centres", centres, (2, Jp)),
-                           ("post", post, (Jp, B)), ("tmp", tmp, (Jp, B)), ("out", out, (W, _L.BAYES_OUT_ROWS, B))):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"{name} must be a contiguous float32 tensor {shape} on loglik's device")
-    if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != dev or \
-            workspace.numel() < bayes_filter_workspace_floats(Jp, B):
-        raise ValueError(f"workspace must be a contiguous float32 tensor of {bayes_filter_workspace_floats(Jp, B)} elements")
-    if restart is not None:
-        if restart.dtype == torch.bool:
-            restart = restart.view(torch.uint8)
-        if restart.dtype != torch.uint8 or tuple(restart.shape) != (W, B) or not restart.is_contiguous() or restart.device != dev:
-            raise ValueError(f"restart must be a contiguous uint8 or bool tensor ({W}, {B}) on loglik's device")
-    radius = len(taps) - 1
-    if not 1 <= radius <= _L.BAYES_FILTER_MAX_RADIUS:
-        raise ValueError(f"taps must hold g[0..R] for a radius R in 1..{_L.BAYES_FILTER_MAX_RADIUS}, got {len(taps)} values")
-    g = (C.c_float * (radius + 1))(*[float(x) for x in taps])
+    named = [(n, t, s) for (n, s), t in zip(_TABLES, (prior, inv_norm, centres))]
+    named += [("post", post, ("Jp", "B")), ("tmp", tmp, ("Jp", "B")), ("out", out, ("W", _L.BAYES_OUT_ROWS, "B"))]
+    W, Jp, B, radius, g, restart = _bayes_scan_args(loglik, taps, named, workspace, bayes_filter_workspace_floats, restart)
     _L.check(_L.lib.riab_bayes_filter(_L.ptr(loglik), W, int(n_bins), Jp, int(ny), int(nx), B, radius, g, float(mixing),
                                       _L.ptr(prior), _L.ptr(inv_norm), _L.ptr(centres),
                                       None if restart is None else _L.ptr(restart), 1 if first else 0, _L.ptr(post),
                                       _L.ptr(tmp), _L.ptr(workspace), _L.ptr(out), _L.current_stream()), "riab_bayes_filter")
+
+
+@_register("bayes_filter_keep(Tensor loglik, int n_bins, int ny, int nx, float[] taps, float mixing, Tensor prior, "
+           "Tensor inv_norm, Tensor centres, Tensor? restart, bool first, Tensor(a!) ells, Tensor(b!) tmp, "
+           "Tensor(c!) workspace, Tensor(d!) out) -> ()",
+           lambda loglik, n_bins, ny, nx, taps, mixing, prior, inv_norm, centres, restart, first, ells, tmp, workspace, out: None)
+def bayes_filter_keep(loglik: Tensor, n_bins: int, ny: int, nx: int, taps: List[float], mixing: float, prior: Tensor,
+                      inv_norm: Tensor, centres: Tensor, restart: Optional[Tensor], first: bool, ells: Tensor, tmp: Tensor,
+                      workspace: Tensor, out: Tensor) -> None:
+    """`bayes_filter` with every window's l kept (riab_bayes_filter_keep): ells float32 (W, Jp, B) stands in post's place,
+    window w going through ells[w]; the same kernels and the same bits in out, tmp and the workspace.  What `bayes_smooth`
+    reads."""
+    named = [(n, t, s) for (n, s), t in zip(_TABLES, (prior, inv_norm, centres))]
+    named += [("ells", ells, ("W", "Jp", "B")), ("tmp", tmp, ("Jp", "B")), ("out", out, ("W", _L.BAYES_OUT_ROWS, "B"))]
+    W, Jp, B, radius, g, restart = _bayes_scan_args(loglik, taps, named, workspace, bayes_filter_workspace_floats, restart)
+    _L.check(_L.lib.riab_bayes_filter_keep(_L.ptr(loglik), W, int(n_bins), Jp, int(ny), int(nx), B, radius, g, float(mixing),
+                                           _L.ptr(prior), _L.ptr(inv_norm), _L.ptr(centres),
+                                           None if restart is None else _L.ptr(restart), 1 if first else 0, _L.ptr(ells),
+                                           _L.ptr(tmp), _L.ptr(workspace), _L.ptr(out), _L.current_stream()),
+             "riab_bayes_filter_keep")
+
+
+@_register("bayes_smooth(Tensor loglik, Tensor ells, Tensor filtered, int n_bins, int ny, int nx, float[] taps, float mixing, "
+           "Tensor prior, Tensor inv_norm, Tensor centres, Tensor? restart, bool last, Tensor(a!) beta, Tensor(b!) tmp, "
+           "Tensor(c!) workspace, Tensor(d!) out) -> ()",
+           lambda loglik, ells, filtered, n_bins, ny, nx, taps, mixing, prior, inv_norm, centres, restart, last, beta, tmp,
+           workspace, out: None)
+def bayes_smooth(loglik: Tensor, ells: Tensor, filtered: Tensor, n_bins: int, ny: int, nx: int, taps: List[float],
+                 mixing: float, prior: Tensor, inv_norm: Tensor, centres: Tensor, restart: Optional[Tensor], last: bool,
+                 beta: Tensor, tmp: Tensor, workspace: Tensor, out: Tensor) -> None:
+    """The backward pass behind `bayes_filter_keep` over W consecutive windows, last to first (riab_bayes_smooth, two launches
+    per window, all issued by one native call): out[t] = the six rows of the smoothed posterior p(x_t | every window of the
+    run), row 4 the filter's; on a window where the chain is cut (the run's last, before a restart or a NaN window, a NaN
+    window) the filter's six rows, copied.  loglik, ells float32 (W, Jp, B) and filtered float32 (W, 6, B): what the filter
+    was given and what it wrote; taps, prior, inv_norm, centres, restart: the filter's; last: these are the run's last
+    windows, else the state in beta / tmp / workspace continues the run to the left (a run is given rightmost first); beta,
+    tmp float32 (Jp, B); workspace float32 of `bayes_smooth_workspace_floats(Jp, B)` elements; out float32 (W, 6, B), written
+    (not `filtered`)."""
+    named = [(n, t, s) for (n, s), t in zip(_TABLES, (prior, inv_norm, centres))]
+    named += [("ells", ells, ("W", "Jp", "B")), ("filtered", filtered, ("W", _L.BAYES_OUT_ROWS, "B")), ("beta", beta, ("Jp", "B")),
+              ("tmp", tmp, ("Jp", "B")), ("out", out, ("W", _L.BAYES_OUT_ROWS, "B"))]
+    W, Jp, B, radius, g, restart = _bayes_scan_args(loglik, taps, named, workspace, bayes_smooth_workspace_floats, restart)
+    if W and out.data_ptr() == filtered.data_ptr():
+        raise ValueError("out must not be the filter's outputs")
+    _L.check(_L.lib.riab_bayes_smooth(_L.ptr(loglik), _L.ptr(ells), _L.ptr(filtered), W, int(n_bins), Jp, int(ny), int(nx), B,
+                                      radius, g, float(mixing), _L.ptr(prior), _L.ptr(inv_norm), _L.ptr(centres),
+                                      None if restart is None else _L.ptr(restart), 1 if last else 0, _L.ptr(beta),
+                                      _L.ptr(tmp), _L.ptr(workspace), _L.ptr(out), _L.current_stream()), "riab_bayes_smooth")
