@@ -17,7 +17,13 @@ kernel walks), so the overrun of one cell group of any kernel stays inside the a
 
 Canaries: "nan" is a quiet NaN with a payload (a kernel that reads its output before writing it, or that skips a store,
 leaves or spreads it; the comparison is on bits), "finite" a value no kernel produces (-7.0: rates are clamped or sums of
-non-negative terms, state rows are positions, unit vectors, speeds).  Bytes (spikes are 0 / 1) get 0xEE and 0xD7.
+non-negative terms, state rows are positions, unit vectors, speeds).  Bytes (spikes are 0 / 1) get 0xEE and 0xD7, 2-byte
+elements (bin ids) 0xBEEF and 0x5A5A.
+
+Two more modes, for the kernels whose contract is not "every element of the output, once":
+
+    arena.check(future, written=mask)              # True: must be written; False: must still hold the canary's bits
+    arena.check(state, inplace=True)               # pre-filled by the test, updated in place: guards (and `other`) only
 
 What this cannot see: reads out of bounds; a stray store that lands INSIDE the view on an element its owner overwrites later
 (the T = 1 cases exist because there every store past the last cell leaves the view); strays further than the guard."""
@@ -28,9 +34,11 @@ MIN_GUARD = 4096
 WIDEST_CHUNK = 64            # cells per workgroup chunk of rate_kernel_generic
 
 # canary bit patterns by element size (bytes); the float ones are the bits of a quiet NaN with a payload / of -7.0
-_BITS = {"nan": {1: 0xEE, 4: 0x7FC0BEEF, 8: 0x7FF80000DEADBEEF},
-         "finite": {1: 0xD7, 4: 0xC0E00000, 8: 0xC01C000000000000}}
-_INT = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
+# 2-byte elements are the rate maps' bin ids (uint16): neither canary is RIAB_RATEMAP_DROPPED (0xFFFF) or a valid bin id
+# (below RIAB_RATEMAP_MAX_BINS = 4096)
+_BITS = {"nan": {1: 0xEE, 2: 0xBEEF, 4: 0x7FC0BEEF, 8: 0x7FF80000DEADBEEF},
+         "finite": {1: 0xD7, 2: 0x5A5A, 4: 0xC0E00000, 8: 0xC01C000000000000}}
+_INT = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
 
 
 def canary_bits(canary, itemsize):
@@ -56,9 +64,12 @@ def coords(rel, shape):
     return tuple(reversed(out))
 
 
+UNTOUCHED = "written where the contract says untouched"
+
+
 class GuardError(AssertionError):
-    """kind: "front guard" | "back guard" | "unwritten" | "canary-dependent"; first, last: the coordinates (see `coords`)
-    of the first and last offending element; count: how many"""
+    """kind: "front guard" | "back guard" | "unwritten" | "canary-dependent" | UNTOUCHED; first, last: the coordinates
+    (see `coords`) of the first and last offending element; count: how many"""
 
     def __init__(self, kind, first, last, count, shape):
         self.kind, self.first, self.last, self.count = kind, first, last, count
@@ -96,9 +107,16 @@ class GuardArena:
         """the whole allocation behind `view` (for a control that writes into the guard on purpose)"""
         return self._slots[view.data_ptr()].buf
 
-    def check(self, view, other=None):
+    def check(self, view, other=None, written=None, inplace=False):
         """Asserts: both guards of `view` are the canary, bit for bit; no interior element is; with `other` (the interior
-        `check` returned for the other canary's run), the two interiors are the same bits.  -> the interior (NumPy)."""
+        `check` returned for the other canary's run), the two interiors are the same bits.  -> the interior (NumPy).
+
+        written: a boolean array of the view's shape, for an output whose contract leaves some elements alone.  Elements
+        with True must not hold the canary ("unwritten"), elements with False must still hold it, bit for bit ("written
+        where the contract says untouched"); `other` compares the True elements only (the others are the two canaries).
+        inplace: the view is state the kernel updates in place and the test pre-filled with real values: the guards are
+        checked, nothing is "unwritten" by its bits, `other` compares the whole interior."""
+        assert written is None or not inplace
         s = self._slots[view.data_ptr()]
         size = s.buf.element_size()
         numel = int(np.prod(s.shape))
@@ -109,16 +127,26 @@ class GuardArena:
             if len(hit):
                 first, last = int(hit[0]) + lo - s.front, int(hit[-1]) + lo - s.front
                 raise GuardError(kind, coords(first, s.shape), coords(last, s.shape), len(hit), s.shape)
-        inner = bits[s.front:s.front + numel]
-        hit = torch.nonzero(inner == word).flatten()
-        if len(hit):
-            raise GuardError("unwritten", coords(int(hit[0]), s.shape), coords(int(hit[-1]), s.shape), len(hit), s.shape)
+        is_canary = (bits[s.front:s.front + numel] == word).cpu().numpy()
+        mask = None
+        if written is not None:
+            mask = np.asarray(written)
+            assert mask.dtype == np.bool_ and mask.shape == s.shape, (mask.dtype, mask.shape, s.shape)
+            mask = mask.reshape(-1)
+        if not inplace:
+            hit = np.nonzero(is_canary if mask is None else is_canary & mask)[0]
+            if len(hit):
+                raise GuardError("unwritten", coords(hit[0], s.shape), coords(hit[-1], s.shape), len(hit), s.shape)
+        if mask is not None:
+            hit = np.nonzero(~is_canary & ~mask)[0]
+            if len(hit):
+                raise GuardError(UNTOUCHED, coords(hit[0], s.shape), coords(hit[-1], s.shape), len(hit), s.shape)
         got = s.view.detach().cpu().numpy().copy()
         if other is not None:
             a = got.reshape(-1).view(f"u{size}")
             b = np.ascontiguousarray(other).reshape(-1).view(f"u{size}")
             assert a.shape == b.shape, (got.shape, np.shape(other))
-            hit = np.nonzero(a != b)[0]
+            hit = np.nonzero(a != b if mask is None else (a != b) & mask)[0]
             if len(hit):
                 raise GuardError("canary-dependent", coords(hit[0], s.shape), coords(hit[-1], s.shape), len(hit), s.shape)
         return got
