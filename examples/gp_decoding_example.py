@@ -4,7 +4,8 @@ The reference's comparison (its decoding_position_example demo and tests/test_ad
 agent in a room with a wall, thresholded PlaceCells and GridCells, both decoders fitted on every 5th row of the first part of
 the run — GaussianProcessRegressor(alpha=0.01, RBF(sqrt(n / 20))) and Ridge(alpha=0.01) — and tested on the rest.  Then 1024
 agents: the GP's training set is chosen from the (row, agent) samples of the recorded history by a deterministic rule, and
-every held-out sample is decoded by one fused kernel; nothing is copied to the host.
+every held-out sample is decoded by one fused kernel; nothing is copied to the host.  A closing section asks for the
+predictive standard deviation beside the mean (`return_std=True`) and prints how the decoded error compares with it.
 
     python examples/gp_decoding_example.py [steps]
 """
@@ -60,3 +61,28 @@ for name, N in pops.items():
     print(f"1024 agents, {name}: GP on {gp.n_samples} of {int(0.8 * steps_b) * 1024} samples fitted in {1e3 * (t1 - t0):.0f} ms, "
           f"{held_out} held-out samples decoded in {1e3 * (t2 - t1):.0f} ms: error {100 * float(err.mean()):.2f} cm "
           f"(worst agent {100 * float(err.max()):.2f} cm); Ridge on every sample {100 * float(ridge.error(t_start=t_split).mean()):.2f} cm")
+
+
+# ---- the predictive standard deviation: one agent, then 1024 --------------------------------------------------------
+def confidence(label, gp, agent, t_split):
+    """decoded error, mean predicted std and the share of held-out samples whose error lies within two predicted std (the
+    std is the GP's, of each target column: an uncalibrated number, printed as it comes)"""
+    mean, std = gp.decode_tensor(t_start=t_split, return_std=True)                  # (T, 2, Bp), (T, Bp) on the device
+    B = agent._B
+    pos = gp._target_tensor(t_split, None)[:, :, :B]
+    err = torch.sqrt(((mean[:, :, :B] - pos) ** 2).sum(dim=1))                      # (T, B)
+    ok = torch.isfinite(err) & torch.isfinite(std[:, :B])
+    err, sd = err[ok], std[:, :B][ok]
+    print(f"{label}: log marginal likelihood {gp.log_marginal_likelihood_:.1f}; decoded error {100 * float(err.mean()):.2f} cm, "
+          f"mean predicted std {100 * float(sd.mean()):.2f} cm, {100 * float((err <= 2 * sd).float().mean()):.1f} % of "
+          f"{int(ok.sum())} samples within two predicted std")
+
+
+np.random.seed(0)
+Ag1 = riab.Agent(Env, {"dt": 0.05})
+PC1 = riab.PlaceCells(Ag1, {"n": 20, "description": "gaussian_threshold", "widths": 0.4})
+Ag1.simulate(steps)
+t1 = Ag1.history["t"]
+confidence("one agent, PlaceCells", riab.fit_gp_decoder([PC1], t_end=t1[int(0.8 * steps)], stride=5), Ag1, t1[int(0.8 * steps)])
+for name, N in pops.items():
+    confidence(f"1024 agents, {name}", N.fit_gp_decoder(t_end=t_split, alpha=0.01, max_samples=2048), Ag, t_split)

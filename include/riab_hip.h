@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RIAB_ABI_VERSION 11    /* (the riab_history_* entry points, riab_history_moments and riab_history_window_counts among them, riab_gp_predict and riab_bayes_decode were added at 11
+#define RIAB_ABI_VERSION 11    /* (the riab_history_* entry points, riab_history_moments and riab_history_window_counts among them, riab_gp_predict, riab_gp_predict_var and riab_bayes_decode were added at 11
                                 * without a bump: they are new exports only; no struct, enum value or existing signature
                                 * changed, so an older binding still loads this library and a newer one finds a missing
                                 * export at load time) */
@@ -1385,6 +1385,34 @@ int riab_history_moments(const RiabMomentInput* inputs, int32_t n_inputs, const 
 #define RIAB_GP_MAX_OUT 4
 int riab_gp_predict(const RiabFFInput* inputs, int32_t n_inputs, const float* sq_train, const float* alpha, int32_t n_out,
                     int32_t n_train, float inv_two_ell2, int64_t T, int64_t B, float* out, riab_stream_t stream);
+
+/* The predictive variance of the same decoder, in sklearn's formulation (GaussianProcessRegressor.predict(return_std=True),
+ * normalize_y=False): with K + alpha I = L L^T and k*_j = k(x*, x_j),
+ *   out_var[t][b] = max(0, 1 - sum over i of (sum over j <= i of (L^-1)[i][j] k*_j)^2)          (k(x*, x*) = 1 for the RBF)
+ * one number per query, the same for every target column; the caller takes the square root.  The terms of the outer sum
+ * are bounded by 1 (the quadratic form with (K + alpha I)^-1 cancels terms of size N / alpha instead).  (A new export at
+ * ABI 11: no struct, enum value or existing signature changes.)  Arguments as riab_gp_predict, and
+ *   linv_t      device float32 [Np][Np]: linv_t[j][i] = (L^-1)[i][j], the inverse Cholesky factor TRANSPOSED.  Contract:
+ *               zero above the diagonal of L^-1 (linv_t[j][i] = 0 for j > i) and zero in the padding (row or column >=
+ *               n_train).  For the columns i of the block that starts at m0 (m0 a multiple of 32 MT; MT = 4 for Np >= 128,
+ *               2 for Np = 64 or 96, 1 for Np = 32) the rows j >= m0 + 32 MT are NEVER READ: the contraction is shortened
+ *               there, not masked.  The rows j < m0 + 32 MT are read, the zeros above the diagonal among them included.
+ *   workspace   device float32 [T][Np][B] (4 T Np B bytes): stage 1 stores every k*_j there, training sample j as the row and
+ *               positions fastest (the layout riab_feedforward reads a population's rates in).  Every element is written:
+ *               rows n_train <= j < Np hold the finite value exp(-|x*|^2 inv_two_ell2) that the zero-padded tables give (the
+ *               zero padding of linv_t multiplies them away); a column whose |x*|^2 is not finite holds NaN in every row.
+ *   out_var     device float32 [T][B]; NaN for a column whose |x*|^2 is not finite, that column alone
+ *   out_mean    device float32 [T][n_out][B] or null: the predictive mean, written by riab_gp_predict's code (same bits)
+ * Two launches on `stream`, nothing allocated or synchronised (capturable).  Stage 1 is riab_gp_predict's kernel with its
+ * block epilogue also storing k*; stage 2 contracts linv_t with the workspace on the same fp32 MFMA core (j ascending),
+ * squares each row's result and adds it into one running sum per position, i ascending within each half-wave and the two
+ * halves added at the end, as the mean's sums are.  No atomics, N is not split over workgroups: the bits of a query depend
+ * on neither T, B, its tile, nor on how the caller splits the work over workspaces.  T = 0 launches nothing.
+ * Checked before anything is launched: everything riab_gp_predict checks (out_mean may be null), and RIAB_EINVAL a null
+ * linv_t, workspace or out_var; RIAB_EALIGN one of them (or out_mean) not 16-byte aligned. */
+int riab_gp_predict_var(const RiabFFInput* inputs, int32_t n_inputs, const float* sq_train, const float* alpha, int32_t n_out,
+                        int32_t n_train, float inv_two_ell2, const float* linv_t, int64_t T, int64_t B, float* workspace,
+                        float* out_var, float* out_mean, riab_stream_t stream);
 
 /* ---- Bayesian (Poisson maximum-likelihood) position decoding from spikes on the device history ---------------------------
  * The decoder of the place-cell literature: spike counts k_c of a time window of duration tau against the cells' tuning

@@ -14,7 +14,18 @@ mean of every (row, agent) sample of the history,
     mean(x*) = sum_j exp(-|x* - x_j|^2 / (2 l^2)) alpha_[j],
 
 goes through `torch.ops.riab.gp_predict` (csrc/riab_gp.hip): one fused kernel on the fp32 matrix cores that never writes
-the (samples x N) kernel matrix to memory.  There is no `as_layer()`: a GP is not a FeedForwardLayer."""
+the (samples x N) kernel matrix to memory.  There is no `as_layer()`: a GP is not a FeedForwardLayer.
+
+With `return_std=True` the predictive standard deviation comes with the mean, in sklearn's own formulation
+(`predict(return_std=True)`): with K + alpha I = L L^T and k*_j = k(x*, x_j),
+
+    var(x*) = 1 - |L^-1 k*|^2,     std = sqrt(max(var, 0))                (k(x*, x*) = 1 for the RBF; NaN stays NaN)
+
+one number per query, the same for every target column.  `torch.ops.riab.gp_predict_var` runs it in two launches: the mean's
+kernel also stores k* into a workspace `[T][Np][B]`, and a second kernel contracts it with the transposed inverse factor
+(`GPDecoder._variance_table`) over the triangular half and sums the squares.  The workspace is the one thing that scales
+with the number of queries, so the work is cut into pieces that fit `max_workspace_bytes`; the result does not depend on
+the cut."""
 import math
 
 import numpy as np
@@ -47,6 +58,22 @@ def select_samples(n_rows, n_agents, max_samples):
     return flat // B, flat % B
 
 
+def workspace_pieces(T, B, Np, max_workspace_bytes):
+    """How `predict_tensor(return_std=True)` cuts T rows of B columns into pieces whose workspace (4 Np bytes per (row,
+    column)) fits `max_workspace_bytes`: [(t0, t1, c0, c1)], every (row, column) once, rows ascending and columns ascending
+    within a row.  Whole rows while one fits; otherwise one row at a time in blocks of columns that are multiples of 128
+    (the kernels' position tile).  Raises ValueError when 128 columns of one row do not fit."""
+    T, B, Np, limit = int(T), int(B), int(Np), int(max_workspace_bytes)
+    rows = limit // (4 * Np * B) if B > 0 else T
+    if rows >= 1:
+        return [(t, min(t + rows, T), 0, B) for t in range(0, T, rows)]
+    cols = limit // (4 * Np) // 128 * 128
+    if cols < 128:
+        raise ValueError(f"max_workspace_bytes = {limit} is too small: one row of {min(B, 128)} columns against {Np} "
+                         f"(padded) training samples needs {4 * Np * min(B, 128)} bytes")
+    return [(t, t + 1, c, min(c + cols, B)) for t in range(T) for c in range(0, B, cols)]
+
+
 def _check_hyper(alpha, length_scale, n_total):
     if not float(alpha) >= 0:
         raise ValueError(f"alpha must be >= 0, got {alpha}")
@@ -63,10 +90,13 @@ def _check_hyper(alpha, length_scale, n_total):
 class GPDecoder(HistoryDecoder):
     """GaussianProcessRegressor(alpha, RBF(length_scale), optimizer=None, normalize_y=False), fitted.  `X_train_` (N, n)
     and `alpha_` (N, D) are float64 tensors on the fit's device; `train_rows` / `train_agents` int64 tensors (history row
-    and agent of every training sample, time-major) or None for a decoder made from bare samples."""
+    and agent of every training sample, time-major) or None for a decoder made from bare samples.
+    `log_marginal_likelihood_` is the float64 log marginal likelihood of the training targets under these hyper-parameters
+    (sklearn's `log_marginal_likelihood_value_`: summed over the target columns), a Python float, or None for a decoder
+    constructed directly: what two choices of `length_scale` or `alpha` are compared with."""
 
     def __init__(self, X, alpha_, length_scale, alpha, widths=None, target="pos", populations=None, train_rows=None,
-                 train_agents=None, n_dropped=0):
+                 train_agents=None, n_dropped=0, log_marginal_likelihood=None):
         self.X_train_, self.alpha_ = X, alpha_
         self.length_scale, self.alpha = float(length_scale), float(alpha)
         self.widths = [int(X.shape[1])] if widths is None else [int(w) for w in widths]
@@ -76,7 +106,9 @@ class GPDecoder(HistoryDecoder):
         self.populations = None if populations is None else list(populations)
         self.train_rows, self.train_agents = train_rows, train_agents
         self.n_samples, self.n_dropped = int(X.shape[0]), int(n_dropped)
+        self.log_marginal_likelihood_ = None if log_marginal_likelihood is None else float(log_marginal_likelihood)
         self._tables = None
+        self._linv_t = None
 
     @classmethod
     def from_samples(cls, X, y, length_scale=None, alpha=0.01, **kw):
@@ -99,12 +131,32 @@ class GPDecoder(HistoryDecoder):
         if int(info.item()) != 0:
             raise ValueError(f"the kernel matrix + alpha I is not positive definite at alpha = {alpha} (leading minor "
                              f"{int(info.item())}): duplicate or nearly equal training samples need a larger alpha")
-        return cls(X, torch.cholesky_solve(y, L), ell, alpha, **kw)
+        alpha_ = torch.cholesky_solve(y, L)
+        # -1/2 y^T alpha_ - sum log L_ii - N/2 log 2 pi per target column, summed over the columns (L is not kept)
+        D = int(y.shape[1])
+        lml = -0.5 * float((y * alpha_).sum()) - D * float(torch.log(L.diagonal()).sum()) - 0.5 * D * N * math.log(2.0 * math.pi)
+        return cls(X, alpha_, ell, alpha, log_marginal_likelihood=lml, **kw)
 
     def mean_float64(self, X):
         """The predictive mean in float64 with torch on X's device, X float64 (S, n) -> (S, D): the definition the kernel is
         checked against, for a handful of samples (it materialises the S x N kernel matrix)."""
         return kernel_matrix(X, self.X_train_.to(X.device), self.length_scale) @ self.alpha_.to(X.device)
+
+    def _factor(self, dev):
+        """L of K + alpha I = L L^T, float64 on `dev`, factorised again from X_train_ (the fit does not keep it)"""
+        X = self.X_train_.to(dev)
+        K = kernel_matrix(X, X, self.length_scale)
+        K.diagonal().add_(self.alpha)
+        return torch.linalg.cholesky(K)
+
+    def std_float64(self, X):
+        """The predictive standard deviation in float64 with torch on X's device, X float64 (S, n) -> (S,): sklearn's
+        sqrt(max(0, 1 - |L^-1 k*|^2)), the definition the kernels are checked against, for a handful of samples (it
+        factorises K + alpha I again and materialises the S x N kernel matrix)."""
+        ks = kernel_matrix(X, self.X_train_.to(X.device), self.length_scale)
+        V = torch.linalg.solve_triangular(self._factor(X.device), ks.T, upper=False)      # (N, S)
+        var = 1.0 - (V * V).sum(dim=0)
+        return torch.sqrt(torch.where(var < 0, torch.zeros_like(var), var))
 
     # ---- running the decoder (riab_gp_predict) ---------------------------------------------------------------------------
     def _populations(self):
@@ -132,20 +184,80 @@ class GPDecoder(HistoryDecoder):
             self._tables = (wts, sq, al)
         return self._tables
 
-    def predict_tensor(self, rates):
+    def _variance_table(self, dev):
+        """linv_t float32 (Np, Np): linv_t[j][i] = (L^-1)[i][j], exactly zero above the diagonal of L^-1 and in the padding:
+        what riab_gp_predict_var reads.  Built on first use (K + alpha I is factorised again in float64 on `dev`, L^-1 taken
+        by a triangular solve against the identity) and kept per device like `_device_tables`: 4 Np^2 bytes, 1 GB at the
+        16 384-sample limit (and four float64 N x N matrices, 8 GB there, while it is built).  Calls without return_std
+        never build it."""
+        if self._linv_t is None or self._linv_t.device != torch.device(dev):
+            N = self.n_samples
+            Np = (N + 31) // 32 * 32
+            eye = torch.eye(N, dtype=torch.float64, device=dev)
+            linv = torch.linalg.solve_triangular(self._factor(dev), eye, upper=False).tril_()
+            del eye
+            table = torch.zeros((Np, Np), dtype=torch.float32, device=dev)
+            table[:N, :N] = linv.T.to(torch.float32)
+            self._linv_t = table
+        return self._linv_t
+
+    def predict_tensor(self, rates, return_std=False, max_workspace_bytes=2 ** 28):
         """The predictive mean of rates that are not in a history: a list of float32 `[T][n_l][Bp]` device tensors, one per
-        population (widths as fitted) -> float32 `[T][D][Bp]`."""
+        population (widths as fitted) -> float32 `[T][D][Bp]`.  return_std=True: (mean `[T][D][Bp]`, std `[T][Bp]`), the
+        mean with the bits it has without the flag.  The kernel values pass through a workspace of 4 Np bytes per (row,
+        column); the work is cut into the `workspace_pieces` that fit `max_workspace_bytes` (whole rows first, then blocks of
+        columns that are multiples of 128, which are copied to make them contiguous), and the result is bit-identical for
+        every cut.  ValueError when 128 columns of one row do not fit `max_workspace_bytes`."""
         rates = list(rates)
         if len(rates) != len(self.widths) or any(int(x.shape[1]) != w for x, w in zip(rates, self.widths)):
             raise ValueError(f"this decoder takes {len(self.widths)} rate tensors (T, n_l, Bp) of widths {self.widths}")
-        wts, sq, al = self._device_tables(rates[0].device)
-        return torch.ops.riab.gp_predict(rates, wts, sq, al, self.n_samples, 1.0 / (2.0 * self.length_scale ** 2))
+        dev = rates[0].device
+        wts, sq, al = self._device_tables(dev)
+        inv = 1.0 / (2.0 * self.length_scale ** 2)
+        if not return_std:
+            return torch.ops.riab.gp_predict(rates, wts, sq, al, self.n_samples, inv)
+        T, B, Np, D = int(rates[0].shape[0]), int(rates[0].shape[2]), int(sq.shape[0]), int(al.shape[0])
+        pieces = workspace_pieces(T, B, Np, max_workspace_bytes)
+        linv_t = self._variance_table(dev)
+        ws = torch.empty(max([(t1 - t0) * Np * (c1 - c0) for t0, t1, c0, c1 in pieces], default=0), dtype=torch.float32,
+                         device=dev)
+        mean = var = None
+        for t0, t1, c0, c1 in pieces:
+            whole = c0 == 0 and c1 == B
+            part = [x[t0:t1] if whole else x[t0:t1, :, c0:c1].contiguous() for x in rates]
+            v, m = torch.ops.riab.gp_predict_var(part, wts, sq, al, linv_t, self.n_samples, inv, ws, True)
+            if len(pieces) == 1:
+                mean, var = m, v
+                break
+            if mean is None:
+                mean = torch.empty((T, D, B), dtype=torch.float32, device=dev)
+                var = torch.empty((T, B), dtype=torch.float32, device=dev)
+            mean[t0:t1, :, c0:c1] = m
+            var[t0:t1, c0:c1] = v
+        if mean is None:      # T = 0
+            mean = torch.empty((T, D, B), dtype=torch.float32, device=dev)
+            var = torch.empty((T, B), dtype=torch.float32, device=dev)
+        return mean, torch.sqrt(var)
 
-    def decode_tensor(self, t_start=None, t_end=None):
+    def decode_tensor(self, t_start=None, t_end=None, return_std=False, max_workspace_bytes=2 ** 28):
         """The decoded target of the history rows `get_history_slice(t_start, t_end)` (both None: every row): float32
-        `[T][D][Bp]` on the device."""
+        `[T][D][Bp]` on the device; return_std=True: (that, the predictive std float32 `[T][Bp]`), as `predict_tensor`."""
         agent, pieces = self._pieces_of_rates(t_start, t_end)
-        return self._joined(agent, [self.predict_tensor(views) for views in pieces])
+        if not return_std:
+            return self._joined(agent, [self.predict_tensor(views) for views in pieces])
+        parts = [self.predict_tensor(views, True, max_workspace_bytes) for views in pieces]
+        if not parts:
+            return self._joined(agent, []), torch.empty((0, agent._Bp), dtype=torch.float32, device=agent._device)
+        return self._joined(agent, [m for m, _ in parts]), self._joined(agent, [s for _, s in parts])
+
+    def decode(self, t_start=None, t_end=None, return_std=False, max_workspace_bytes=2 ** 28):
+        """`decode_tensor` on the host: NumPy (T, B, D), or (T, D) for one agent; return_std=True: (that, std (T, B) or (T,))."""
+        if not return_std:
+            return super().decode(t_start, t_end)
+        agent = self._populations()[0].Agent
+        mean, std = self.decode_tensor(t_start, t_end, True, max_workspace_bytes)
+        m, s = mean[:, :, :agent._B].permute(0, 2, 1).cpu().numpy(), std[:, :agent._B].cpu().numpy()
+        return (m[:, 0], s[:, 0]) if agent._B == 1 else (m, s)
 
 
 def kernel_matrix(A, B, length_scale):

@@ -271,6 +271,9 @@ PROTOTYPES = {
                                        C.c_void_p]),
     "riab_gp_predict": (C.c_int, [C.POINTER(RiabFFInput), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
                                   C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "riab_gp_predict_var": (C.c_int, [C.POINTER(RiabFFInput), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_float, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
     "riab_history_window_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
                                              C.c_void_p, C.c_void_p]),
     "riab_bayes_decode": (C.c_int, [C.POINTER(RiabFFInput), C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,

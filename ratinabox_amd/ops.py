@@ -17,6 +17,7 @@ Functional operators (return a new tensor)
     feedforward                                                         float32 (T, n_out, B)
     mlp_forward   a whole multi-layer perceptron in one launch (contribs.NeuralNetworkNeurons)   float32 (T, n_out, B)
     gp_predict    the predictive mean of an RBF Gaussian-process decoder over rate rows                 float32 (T, D, B)
+    gp_predict_var  its predictive variance (and the mean) through a workspace of kernel values   float32 (T, B), (T, D, B)
     bayes_decode  Poisson maximum-likelihood position decoding of spike counts (or rates) over bins       float32 (T, 6, B)
 In-place operators
     history_window_counts  spike rows of a history piece added into the uint8 counts of their time windows
@@ -654,21 +655,12 @@ def history_moments(inputs: List[Tensor], traj: Tensor, target_rows: List[int], 
 
 
 # ---- Gaussian-process decoders over history rows: riab_gp_predict -----------------------------------------------------
-@_register("gp_predict(Tensor[] inputs, Tensor[] train_t, Tensor sq_train, Tensor alpha, int n_train, float inv_two_ell2) "
-           "-> Tensor", lambda inputs, train_t, sq_train, alpha, n_train, inv_two_ell2:
-           inputs[0].new_empty((inputs[0].shape[0], alpha.shape[0], inputs[0].shape[2])))
-def gp_predict(inputs: List[Tensor], train_t: List[Tensor], sq_train: Tensor, alpha: Tensor, n_train: int,
-               inv_two_ell2: float) -> Tensor:
-    """The predictive mean of an RBF Gaussian process over rate rows (riab_gp_predict: fp32 matrix cores, exponential and
-    alpha contraction fused): out[t][d][b] = sum_{j < n_train} exp(-max(0, |x*|^2 + |x_j|^2 - 2 x*.x_j) inv_two_ell2)
-    alpha[d][j], x* the concatenated inputs_l[t, :, b].  inputs_l float32 (T, n_l, B); train_t_l float32 (n_l, Np): the
-    training matrix of input l TRANSPOSED, Np = n_train rounded up to 32, zero padded; sq_train float32 (Np,) = |x_j|^2;
-    alpha float32 (D, Np), D = 1..4, zero padded.  Returns float32 (T, D, B)."""
+def _gp_args(inputs, train_t, sq_train, alpha, n_train):
+    """The checks gp_predict and gp_predict_var share -> (the RiabFFInput array, T, B, D, Np, device)"""
     if not inputs or len(inputs) != len(train_t) or len(inputs) > 8:
         raise ValueError("1..8 inputs, one transposed training matrix each")
     T, _, B = (int(x) for x in inputs[0].shape)
-    n_train = int(n_train)
-    Np = (n_train + 31) // 32 * 32
+    Np = (int(n_train) + 31) // 32 * 32
     dev = inputs[0].device
     arr = (_L.RiabFFInput * len(inputs))()
     for l, (x, w) in enumerate(zip(inputs, train_t)):
@@ -684,11 +676,50 @@ def gp_predict(inputs: List[Tensor], train_t: List[Tensor], sq_train: Tensor, al
     if alpha.dtype != torch.float32 or alpha.dim() != 2 or alpha.shape[1] != Np or not alpha.is_contiguous() or \
             alpha.device != dev:
         raise ValueError(f"alpha must be a contiguous float32 tensor (D, {Np}) on the inputs' device")
-    D = int(alpha.shape[0])
+    return arr, T, B, int(alpha.shape[0]), Np, dev
+
+
+@_register("gp_predict(Tensor[] inputs, Tensor[] train_t, Tensor sq_train, Tensor alpha, int n_train, float inv_two_ell2) "
+           "-> Tensor", lambda inputs, train_t, sq_train, alpha, n_train, inv_two_ell2:
+           inputs[0].new_empty((inputs[0].shape[0], alpha.shape[0], inputs[0].shape[2])))
+def gp_predict(inputs: List[Tensor], train_t: List[Tensor], sq_train: Tensor, alpha: Tensor, n_train: int,
+               inv_two_ell2: float) -> Tensor:
+    """The predictive mean of an RBF Gaussian process over rate rows (riab_gp_predict: fp32 matrix cores, exponential and
+    alpha contraction fused): out[t][d][b] = sum_{j < n_train} exp(-max(0, |x*|^2 + |x_j|^2 - 2 x*.x_j) inv_two_ell2)
+    alpha[d][j], x* the concatenated inputs_l[t, :, b].  inputs_l float32 (T, n_l, B); train_t_l float32 (n_l, Np): the
+    training matrix of input l TRANSPOSED, Np = n_train rounded up to 32, zero padded; sq_train float32 (Np,) = |x_j|^2;
+    alpha float32 (D, Np), D = 1..4, zero padded.  Returns float32 (T, D, B)."""
+    arr, T, B, D, _, dev = _gp_args(inputs, train_t, sq_train, alpha, n_train)
     out = torch.empty((T, D, B), dtype=torch.float32, device=dev)
-    _L.check(_L.lib.riab_gp_predict(arr, len(inputs), _L.ptr(sq_train), _L.ptr(alpha), D, n_train, float(inv_two_ell2), T, B,
-                                    _L.ptr(out), _L.current_stream()), "riab_gp_predict")
+    _L.check(_L.lib.riab_gp_predict(arr, len(inputs), _L.ptr(sq_train), _L.ptr(alpha), D, int(n_train), float(inv_two_ell2), T,
+                                    B, _L.ptr(out), _L.current_stream()), "riab_gp_predict")
     return out
+
+
+@_register("gp_predict_var(Tensor[] inputs, Tensor[] train_t, Tensor sq_train, Tensor alpha, Tensor linv_t, int n_train, "
+           "float inv_two_ell2, Tensor(a!) workspace, bool with_mean=True) -> (Tensor, Tensor)",
+           lambda inputs, train_t, sq_train, alpha, linv_t, n_train, inv_two_ell2, workspace, with_mean=True:
+           (inputs[0].new_empty((inputs[0].shape[0], inputs[0].shape[2])),
+            inputs[0].new_empty((inputs[0].shape[0], alpha.shape[0] if with_mean else 0, inputs[0].shape[2]))))
+def gp_predict_var(inputs: List[Tensor], train_t: List[Tensor], sq_train: Tensor, alpha: Tensor, linv_t: Tensor, n_train: int,
+                   inv_two_ell2: float, workspace: Tensor, with_mean: bool = True):
+    """The predictive variance of an RBF Gaussian process over rate rows, in sklearn's formulation (riab_gp_predict_var, two
+    launches): var[t][b] = max(0, 1 - |L^-1 k*|^2), k*_j the kernel value gp_predict sums.  Arguments as gp_predict, and
+    linv_t float32 (Np, Np): linv_t[j][i] = (L^-1)[i][j] of K + alpha I = L L^T, zero above the diagonal of L^-1 and in the
+    padding; workspace: a contiguous float32 tensor of at least T Np B elements, overwritten with k* as (T, Np, B).  Returns
+    (var float32 (T, B), mean float32 (T, D, B) with gp_predict's bits, or (T, 0, B) with with_mean=False)."""
+    arr, T, B, D, Np, dev = _gp_args(inputs, train_t, sq_train, alpha, n_train)
+    if linv_t.dtype != torch.float32 or tuple(linv_t.shape) != (Np, Np) or not linv_t.is_contiguous() or linv_t.device != dev:
+        raise ValueError(f"linv_t must be a contiguous float32 tensor ({Np}, {Np}) on the inputs' device")
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != dev or \
+            workspace.numel() < T * Np * B:
+        raise ValueError(f"workspace must be a contiguous float32 tensor of at least T Np B = {T * Np * B} elements")
+    var = torch.empty((T, B), dtype=torch.float32, device=dev)
+    mean = torch.empty((T, D if with_mean else 0, B), dtype=torch.float32, device=dev)
+    _L.check(_L.lib.riab_gp_predict_var(arr, len(inputs), _L.ptr(sq_train), _L.ptr(alpha), D, int(n_train), float(inv_two_ell2),
+                                        _L.ptr(linv_t), T, B, _L.ptr(workspace), _L.ptr(var),
+                                        _L.ptr(mean) if with_mean else None, _L.current_stream()), "riab_gp_predict_var")
+    return var, mean
 
 
 # ---- Bayesian decoding from spikes: riab_history_window_counts, riab_bayes_decode --------------------------------------
